@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: LQR timestep-solves/sec @ batch=4096, T=50, n_x=8, n_u=2 (BASELINE.json).
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,9 @@ materialised in HBM) over one batch of synthetic trajectories resident in HBM (n
 Cache: consecutive steps solve different input sets).  With N
 GPUs every rank solves its own shard of B trajectories (independent units, no data-path
 collective; `--gather` adds the RCCL all-gather of (x*, u*) to the timed region), so scaling is
-weak and `value` = N*B*T*K / max-over-ranks time.  Rank 0 prints ONE JSON line.
+weak and `value` = N*B*T*K / max-over-ranks time.  The timed region is ONE run of exactly K steps after an untimed
+run-up and W warm-up steps; `ms_per_step` is its time over K.  Rank 0 prints ONE JSON line; with `--dump-outputs DIR` it
+also writes the (x*, u*) that the last timed step produced to DIR/x.npy and DIR/u.npy.
 
 Extra objects in that line:
   roofline     dominant kernel vs the HBM roof: algorithmic bytes per launch (832 B per
@@ -52,6 +54,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s s
 MFMA_F32_PEAK_TFLOPS = 157.3  # dense fp32 matrix peak (MI355X_MICROARCH.md)
 PARITY_TOL = 1e-4
 INFINITY_CACHE_BYTES = 256 * 2 ** 20
+DUMP_BYTES = 64 * 10 ** 6      # --dump-outputs: at most this much in all
 
 WORKLOADS = {
     # name: (B per GPU, T, nx, nu)
@@ -617,6 +620,25 @@ def secondary_f64(device, d):
             "float32_stream_vs_this": {"max_rel_err_x": ex, "max_rel_err_u": eu, "tolerance": PARITY_TOL}}
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array (time-major [T, batch, ...], float32) as out_dir/<name>.npy.  Where the arrays together exceed
+    DUMP_BYTES, the same fixed sample of trajectories (numpy seed 0, sorted) is taken from every one of them.  Returns what was
+    written, for the JSON line."""
+    os.makedirs(out_dir, exist_ok=True)
+    batch = next(iter(arrays.values())).shape[1]
+    per_traj = sum(a.numel() // batch * 4 for a in arrays.values())
+    keep = min(batch, (DUMP_BYTES - 4096 * len(arrays)) // per_traj)     # (4096: room for each file's header)
+    idx = None
+    if keep < batch:
+        idx = np.sort(np.random.default_rng(0).choice(batch, keep, replace=False))
+    for name, a in arrays.items():
+        if idx is not None:
+            a = a.index_select(1, torch.as_tensor(idx, device=a.device))
+        np.save(os.path.join(out_dir, name + ".npy"), a.detach().to(torch.float32).cpu().numpy())
+    return {"dir": out_dir, "arrays": sorted(arrays), "trajectories": int(keep), "of": int(batch),
+            "sample": None if idx is None else "numpy default_rng(0).choice(%d, %d, replace=False), sorted" % (batch, keep)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -635,7 +657,12 @@ def main():
                     "before the warm-up steps (the first milliseconds of a job instead of its steady rate)")
     ap.add_argument("--allow-secondary-failure", action="store_true",
                     help="exit 0 even when a secondary measurement raised (its error string is in the JSON line either way)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (x*, u*: float32, time-major) as DIR/x.npy and DIR/u.npy; "
+                    "a batch beyond %d MB is a fixed sample of trajectories (numpy seed 0), the same in every run" % (DUMP_BYTES // 10 ** 6))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -701,74 +728,54 @@ def main():
             solve_device(e["C"], e["c"], e["F"], e["f"], e["x_init"], None, T, nx, nu, out=(xs, us))
             pipe.gather(k)
 
-    # For the record, the contract's protocol from a cold device first (W warm-up steps, K timed ones - a window of a
-    # millisecond at the driver's K = 20): reported as `cold_start`, never as `value`
-    cold = None
-    if not args.no_settle:
-        step()
-        torch.cuda.synchronize()       # (first-call costs are not part of either figure)
-        for _ in range(args.warmup):
-            step()
-        torch.cuda.synchronize()
-        c0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        cold = (time.perf_counter() - c0) / args.steps
     # the device in the power state of a running job (every rank its own GPU), then the contract's W warm-up steps
     # (with --gather the step holds a collective: every rank runs the same, fixed number of blocks)
     # (the run-up is >= 60 ms of the same launch back to back: the sensors, which the SMU refreshes every few milliseconds, have
-    # time to show the state the timed blocks then run in - the blocks themselves are ~1 ms each)
+    # time to show the state the timed steps then run in)
     with ClockSampler(device.index or 0) as run_up_clocks:
         pre_calls, pre_ms, pre_times = (0, 0.0, [None, None]) if args.no_settle else settle(
             step, fixed_blocks=(80 if B * T * (nx + nu) ** 2 < 1e8 else 4) if gx is not None else None)
     run_up_clock_info = None if args.no_settle else run_up_clocks.summary()
+    # the run-up makes as many calls as the clocks need: a few more bring the rotation back to set 0, so that the step the
+    # timed region ends with solves the same input set in every run with the same arguments (--dump-outputs)
+    while k_step[0] % n_sets:
+        step()
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    # The timed region, kBlocks times: EXACTLY K steps bracketed by a barrier + torch.cuda.synchronize() on both sides, the MAX
-    # over ranks of each block's time; `value` is the MEDIAN block (one block of K = 20 is 0.7 ms of a 20 s run: one number from
-    # it says little, the spread of eleven says whether a box is steady), min and max travel in `roofline.blocks`.  Kernel
-    # duration: ONE pair of HIP events on the launch stream (torch's current stream) around the K back-to-back launches of each
-    # block; span / K = average launch duration incl. boundaries.
-    kBlocks = 11
-    block_wall, block_ev = [], []
+    # The timed region: EXACTLY K steps bracketed by a barrier + torch.cuda.synchronize() on both sides, the MAX over ranks of
+    # its time.  Kernel duration: ONE pair of HIP events on the launch stream (torch's current stream) around the K
+    # back-to-back launches; span / K = average launch duration incl. boundaries.
     with ClockSampler(device.index or 0) as clocks:
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(kBlocks)]
-        for blk in range(kBlocks):
-            # every block is the contract's whole protocol: W untimed warm-up steps, barrier + synchronize, K timed steps,
-            # synchronize + barrier (the device goes from its warm-up straight into the timed steps, as in a running job)
-            for _ in range(args.warmup if blk > 0 else 0):       # (block 0's warm-up ran above)
-                step()
-            torch.cuda.synchronize()
-            if dist is not None:
-                dist.barrier()
-            torch.cuda.synchronize()
-            ev0, ev1 = evs[blk]
-            t0 = time.perf_counter()
-            ev0.record()
-            for _ in range(args.steps):
-                step()
-            ev1.record()
-            torch.cuda.synchronize()
-            if dist is not None:
-                dist.barrier()
-            torch.cuda.synchronize()
-            el = time.perf_counter() - t0
-            if dist is not None:
-                tmax = torch.tensor([el], dtype=torch.float64, device=red_dev)
-                dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-                el = float(tmax.item())
-            block_wall.append(el)
-            block_ev.append(ev0.elapsed_time(ev1) * 1e-3 / args.steps)
-    order = sorted(range(kBlocks), key=lambda i: block_wall[i])
-    mid = order[kBlocks // 2]
-    elapsed = block_wall[mid]
-    kern_s = block_ev[mid]
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        ev0.record()
+        for _ in range(args.steps):
+            step()
+        ev1.record()
+        torch.cuda.synchronize()
+        if dist is not None:
+            dist.barrier()
+        torch.cuda.synchronize()
+        elapsed = time.perf_counter() - t0
+        if dist is not None:
+            tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            elapsed = float(tmax.item())
+        kern_s = ev0.elapsed_time(ev1) * 1e-3 / args.steps
     clock_info = clocks.summary()
+    # what the last timed step handed its caller (rank 0): x*, u* of this rank's solve, or with --gather the all-gathered
+    # (x*, u*) of every rank in the reference's time-major layout
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        if pipe is None:
+            dumped = dump_outputs(args.dump_outputs, {"x": x, "u": u})
+        else:
+            gxs, gus = pipe.result(k_step[0] - 1)
+            dumped = dump_outputs(args.dump_outputs, {"x": GatherPipeline.as_time_major(gxs), "u": GatherPipeline.as_time_major(gus)})
     kern_name = kernel_name() if gx is None else None      # (with --gather the last launch is RCCL's, not ours)
     gather_info = None
     if pipe is not None:
@@ -862,7 +869,7 @@ def main():
             # `frac` is the SMALLER of the two clocks' figures: HIP events on the launch stream around the K timed launches
             # (`frac_events`) and the host's wall clock around the same region incl. the final synchronisation
             # (`frac_wall`, from `ms_per_step`).  The protocol of the measurement travels inside this object (the driver's
-            # parsed record keeps `roofline` whole): the untimed run-up and what the same W + K steps take from a cold start.
+            # parsed record keeps `roofline` whole): the untimed run-up, then W warm-up steps and the K timed ones.
             "roofline": {"bound": "hbm", "achieved": min(achieved, alg_bytes / (elapsed / args.steps) / 1e9),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": min(achieved, alg_bytes / (elapsed / args.steps) / 1e9) / HBM_PEAK_GBS,
@@ -870,31 +877,16 @@ def main():
                          "frac_wall": alg_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": kern_name,
-                         "blocks": {"n": kBlocks, "steps_each": args.steps,
-                                    "ms_per_step_min": min(block_wall) / args.steps * 1e3,
-                                    "ms_per_step_median": elapsed / args.steps * 1e3,
-                                    "ms_per_step_max": max(block_wall) / args.steps * 1e3,
-                                    "kernel_ms_min": min(block_ev) * 1e3, "kernel_ms_max": max(block_ev) * 1e3,
-                                    "ms_per_step_in_order": [round(w / args.steps * 1e3, 5) for w in block_wall],
-                                    "kernel_ms_in_order": [round(e * 1e3, 5) for e in block_ev],
-                                    "what": "value / ms_per_step / frac are the MEDIAN of n timed regions of exactly K steps each "
-                                            "(barrier + synchronize on both sides, max over ranks)"},
                          "clocks": clock_info,
                          "clocks_run_up": run_up_clock_info,
                          "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": kern_s * 1e3,
                          "kernel_ms_wall": elapsed / args.steps * 1e3,
                          "protocol": "value/frac are taken AFTER an untimed run-up of the same step to the device's steady "
                                      "clocks (device_run_up_steps launches, device_run_up_ms), then the contract's W warm-up and "
-                                     "K timed steps; cold_start_ms_per_step is the same W + K protocol run before the run-up",
-                         "device_run_up_steps": pre_calls, "device_run_up_ms": pre_ms,
-                         "cold_start_ms_per_step": None if cold is None else cold * 1e3,
-                         "cold_start_frac": None if cold is None else alg_bytes / cold / 1e9 / HBM_PEAK_GBS},
+                                     "ONE timed region of exactly K steps",
+                         "device_run_up_steps": pre_calls, "device_run_up_ms": pre_ms},
             # what ran on the device before the W warm-up steps and the K timed ones: the same step, untimed, until its
             # time had settled (the steady power state of a running job; scripts/clock_ramp.py has the ramp)
-            "cold_start": None if cold is None else {
-                "ms_per_step": cold * 1e3, "value": B * T / cold,
-                "what": "rank 0's own W warm-up + K timed steps BEFORE the run-up, i.e. in the first milliseconds after the "
-                        "device wakes (its clocks still ramping): what `value` would be without `device_run_up`"},
             "device_run_up": {"untimed_steps": pre_calls, "ms": pre_ms,
                               "ms_per_step_first_block_cold": None if pre_times[0] is None else pre_times[0] * 1e3,
                               "ms_per_step_last_block": None if pre_times[1] is None else pre_times[1] * 1e3,
@@ -920,6 +912,8 @@ def main():
                                                      "(MI355X_MICROARCH.md: 6290); boxes of the pool differ"})
         if gather_info is not None:
             out["gather"] = gather_info
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
         parity_ok, secondary_failed = True, False
         if cb is not None:
             out["cpu_baseline"] = cb

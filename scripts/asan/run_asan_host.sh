@@ -14,8 +14,8 @@ for f in $CS/*.hip; do
 done
 wait $pids
 hipcc $FLAGS -c $REPO/scripts/asan/asan_host_driver.cpp -o $W/driver.o 2> $W/driver.log
-hipcc --offload-arch=gfx950 -fsanitize=address,undefined $W/*.o -o $W/asan_host_driver 2> $W/link.log || { cat $W/link.log | tail -20; exit 2; }
-{ echo "# scripts/asan/run_asan_host.sh: host pass of every *_api.hip built with -fsanitize=address,undefined, driver on the CPU (no GPU)";
+hipcc --offload-arch=gfx950 -fsanitize=address,undefined -fno-gpu-sanitize $W/*.o -o $W/asan_host_driver 2> $W/link.log || { cat $W/link.log | tail -20; exit 2; }
+{ echo "# scripts/asan/run_asan_host.sh: host pass of every *_api.hip built with AddressSanitizer + UBSan, driver on the CPU (no GPU)";
   echo "# library sources: $(python3 -c "import sys; sys.path.insert(0, '$CS'); import build; print(build.source_hash())")";
   ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 HIP_VISIBLE_DEVICES=-1 $W/asan_host_driver 2>&1 | tail -30;
   echo "exit code: ${PIPESTATUS[0]}"; } > $OUT

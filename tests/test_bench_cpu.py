@@ -97,3 +97,30 @@ def test_config5_is_a_strong_scaling_workload():
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert '"scaling": "weak" if strong_total is None else "strong"' in src
     assert '"global_batch": world * B' in src
+
+
+def test_dump_outputs_writes_float32_within_the_cap_and_samples_the_same_trajectories(tmp_path, monkeypatch):
+    """`--dump-outputs`: every array as <name>.npy in float32; a batch beyond the cap is the same seeded sample of trajectories
+    in every array and on every call"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    T, B = 5, 1000
+    x = torch.arange(T * B * 3, dtype=torch.float32).reshape(T, B, 3)
+    u = -torch.arange(T * B * 2, dtype=torch.float32).reshape(T, B, 2)
+    info = bench.dump_outputs(str(tmp_path / "whole"), {"x": x, "u": u})
+    assert info["trajectories"] == B and info["sample"] is None
+    assert np.array_equal(np.load(str(tmp_path / "whole" / "x.npy")), x.numpy())
+    assert np.load(str(tmp_path / "whole" / "u.npy")).dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096 * 2 + T * 5 * 4 * 100)        # room for 100 trajectories
+    a = bench.dump_outputs(str(tmp_path / "a"), {"x": x, "u": u})
+    b = bench.dump_outputs(str(tmp_path / "b"), {"x": x, "u": u})
+    assert a["trajectories"] == 100 and a["of"] == B and a == dict(b, dir=a["dir"])
+    xa, ua = np.load(str(tmp_path / "a" / "x.npy")), np.load(str(tmp_path / "a" / "u.npy"))
+    assert xa.shape == (T, 100, 3) and ua.shape == (T, 100, 2)
+    assert np.array_equal(xa, np.load(str(tmp_path / "b" / "x.npy")))
+    rows = (xa[0, :, 0] / 3).astype(int)                        # x[0, b, 0] = 3 b: the trajectories kept, in order
+    assert np.all(np.diff(rows) > 0) and np.array_equal(ua[0, :, 0], -2.0 * rows)
+    total = sum(os.path.getsize(str(tmp_path / "a" / n)) for n in ("x.npy", "u.npy"))
+    assert total <= bench.DUMP_BYTES

@@ -371,6 +371,30 @@ def test_config5_shard_properties_and_sampled_oracle():
     assert_close(npy(u.index_select(1, idx)), ur, TOL_PRIMAL, "u")
 
 
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` in a fresh process: K timed steps, and x.npy / u.npy are bit for bit the solve of the input
+    set the last of them used (the rotation over input sets restarts at set 0 before the W warm-up steps)"""
+    import json
+    import subprocess
+    import sys
+    import bench
+    W, K = 1, 6
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                        "--workload", "pendulum", "--no-secondary", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == K and line["ms_per_step"] > 0 and line["outputs_dumped"]["arrays"] == ["u", "x"]
+    B, T, nx, nu = bench.WORKLOADS["pendulum"]
+    k = (W + K - 1) % line["roofline"]["input_sets_in_rotation"]
+    _, d = bench.make_inputs(B, T, nx, nu, 0 if k == 0 else 1000 + k, torch.device("cuda"))
+    x, u, _, _ = solve_device(d["C"], d["c"], d["F"], d["f"], d["x_init"], None, T, nx, nu)
+    xd, ud = np.load(str(tmp_path / "x.npy")), np.load(str(tmp_path / "u.npy"))
+    assert xd.dtype == np.float32 and xd.shape == (T, B, nx) and ud.shape == (T, B, nu)
+    assert np.array_equal(xd, npy(x)) and np.array_equal(ud, npy(u))
+
+
 def test_reference_style_dynamics_still_within_primal_tolerance():
     """A = I + 0.2*randn (the reference's initialiser, rho(A) > 1): x,u stay within 1e-4"""
     B, T, nx, nu = 32, 50, 8, 2
