@@ -17,6 +17,11 @@ LIB_PATH = os.environ.get("DMPC_LIB", os.path.join(_HERE, LIB_NAME))
 ABI_VERSION = 411           # include/dmpc.h: DMPC_VERSION the signatures below were written for
 E_BADARG, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3
 INFO_SINGULAR, INFO_NONFINITE, INFO_QP_ITERCAP, INFO_LS_ITERCAP = 1, 2, 4, 8
+# the codes of dmpc_lqr_kernel_family, dmpc_lqr_solve_path and dmpc_lqr_f64_path (include/dmpc.h: DMPC_<name>)
+LQR_FAMILY_ROW16, LQR_FAMILY_WAVE, LQR_FAMILY_GENERIC, LQR_FAMILY_CONTAINER, LQR_FAMILY_TILED = 1, 2, 3, 4, 5
+LQR_PATH_GENERIC, LQR_PATH_PREFETCH, LQR_PATH_DMA, LQR_PATH_ASM_RING, LQR_PATH_ASM_STASH = 0, 1, 2, 3, 4
+LQR_PATH_WAVE_MFMA, LQR_PATH_ASM_WS, LQR_PATH_CONTAINER, LQR_PATH_TILED, LQR_PATH_WIDE = 5, 6, 7, 8, 9
+F64_PATH_LANE, F64_PATH_ROW16, F64_PATH_WAVE = 0, 1, 2
 
 _c_f = ctypes.c_void_p      # const float* / float* (device)
 _c_i = ctypes.c_int

@@ -5,8 +5,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <map>
 #include <mutex>
-#include <unordered_map>
+#include <utility>
 
 namespace dmpc {
 
@@ -15,16 +16,19 @@ static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t
 
 static constexpr size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, set once per kernel (and again only for a larger request), not per
-// launch: the call costs a few microseconds of host time, as much as the launch it precedes
+// hipFuncAttributeMaxDynamicSharedMemorySize of a kernel, set once per (device, kernel) - the attribute belongs to the current
+// device - and again only for a larger request, not per launch: the call costs a few microseconds of host time, as much as the
+// launch it precedes
 inline void set_max_lds(const void *kernel, int bytes) {
   static std::mutex m;
-  static std::unordered_map<const void *, int> done;
+  static std::map<std::pair<int, const void *>, int> done;
+  int device = 0;
+  (void)hipGetDevice(&device);
   std::lock_guard<std::mutex> g(m);
-  auto it = done.find(kernel);
-  if (it != done.end() && it->second >= bytes) return;
+  int &set = done[{device, kernel}];
+  if (set >= bytes) return;
   (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  done[kernel] = bytes;
+  set = bytes;
 }
 
 // The kernel this thread launched last, for dmpc_last_kernel_name() (diagnostics and benchmark labelling: the name a

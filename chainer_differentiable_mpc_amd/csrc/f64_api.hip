@@ -15,10 +15,10 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 
 #include "../../include/dmpc.h"
 #include "api_util.hpp"
+#include "knobs.hpp"
 #include "f64_row_kernels.hpp"
 #include "lqr_tile16_f64.hpp"
 
@@ -314,8 +314,7 @@ static int launch_f64_row_costate(int nx, int nu, const F64RowCostate &a, hipStr
 // the plain fused solve of the large shapes on v_mfma_f64_16x16x4_f64 tiles (lqr_tile16_f64.hpp); DMPC_E_UNSUPPORTED - nothing
 // launched - for other shapes, the clamped solve and the split-c second solve.  DMPC_NO_F64_TILE16=1: off (A/B timing).
 static int launch_f64_tile16(int nx, int nu, const F64RowSolve &a, hipStream_t stream) {
-  static const bool off = [] { const char *e = getenv("DMPC_NO_F64_TILE16"); return e && e[0] == '1'; }();
-  if (off || a.mask != nullptr || a.Ks == nullptr || a.ks == nullptr) return DMPC_E_UNSUPPORTED;
+  if (knob_on<Knob::DMPC_NO_F64_TILE16>() || a.mask != nullptr || a.Ks == nullptr || a.ks == nullptr) return DMPC_E_UNSUPPORTED;
   if (!aligned16(a.C) || !aligned16(a.c) || !aligned16(a.c_u) || !aligned16(a.F) || !aligned16(a.f)) return DMPC_E_UNSUPPORTED;
 #define X(NX_, NU_)                                                                                                    \
   if (nx == NX_ && nu == NU_) {                                                                                        \
@@ -330,11 +329,6 @@ static int launch_f64_tile16(int nx, int nu, const F64RowSolve &a, hipStream_t s
   return DMPC_E_UNSUPPORTED;
 }
 
-static bool f64_row_off() {
-  static const bool off = [] { const char *e = getenv("DMPC_NO_F64_ROW"); return e && e[0] == '1'; }();
-  return off;
-}
-
 }  // namespace dmpc
 
 using namespace dmpc;
@@ -343,12 +337,12 @@ extern "C" {
 
 int dmpc_lqr_f64_path(int nx, int nu) {
   if (nx <= 0 || nu <= 0) return DMPC_E_BADARG;
-  if (!f64_row_off()) {
-#define X(NX_, NU_, L_) if (nx == NX_ && nu == NU_) return L_ == 16 ? 1 : 2;
+  if (!knob_on<Knob::DMPC_NO_F64_ROW>()) {
+#define X(NX_, NU_, L_) if (nx == NX_ && nu == NU_) return L_ == 16 ? DMPC_F64_PATH_ROW16 : DMPC_F64_PATH_WAVE;
     DMPC_F64_ROW_SHAPES(X)
 #undef X
   }
-  return 0;
+  return DMPC_F64_PATH_LANE;
 }
 
 size_t dmpc_lqr_f64_workspace_bytes(int T, int B, int nx, int nu) {
@@ -373,7 +367,7 @@ int dmpc_lqr_solve_f64(int T, int B, int nx, int nu, const double *C, const doub
   double *area = reinterpret_cast<double *>(p);
   p += round256((f64_solve_ws_elems(nx, nu) + 4 * (size_t)nx) * B * sizeof(double)) + round256((size_t)T * B * ns * sizeof(double));
   double *gains = reinterpret_cast<double *>(p);
-  if (!f64_row_off()) {   // the register-resident kernel where the shape has one; gains through the workspace only when LDS is short
+  if (!knob_on<Knob::DMPC_NO_F64_ROW>()) {   // the register-resident kernel where the shape has one; gains through the workspace only when LDS is short
     F64RowSolve r{T, B, C, c, F, f, x_init, nullptr, u_zero_mask, Ks_out, ks_out, x_out, u_out, info, 1};
     const int lanes = nx + nu + 1 <= 16 ? 16 : 64;
     if ((size_t)(256 / lanes) * T * nu * (nx + 1) * sizeof(double) > kMaxLds && Ks_out == nullptr) {
@@ -416,7 +410,7 @@ int dmpc_lqr_kkt_grad_f64(int T, int B, int nx, int nu, const double *C, const d
   double *gains = reinterpret_cast<double *>(p);
   double *dxs = dtau, *dus = dtau + (size_t)T * B * nx;
   // the second solve: same C, F; c = [grad_x; grad_u] (two arrays), f = 0, x_init = 0    differentiable_lqr.py:108-114
-  if (!f64_row_off()) {
+  if (!knob_on<Knob::DMPC_NO_F64_ROW>()) {
     F64RowSolve r{T, B, C, grad_x, F, nullptr, nullptr, grad_u, nullptr, nullptr, nullptr, dxs, dus, info, 1};
     const int lanes = nx + nu + 1 <= 16 ? 16 : 64;
     if ((size_t)(256 / lanes) * T * nu * (nx + 1) * sizeof(double) > kMaxLds) {

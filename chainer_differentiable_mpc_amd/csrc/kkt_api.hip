@@ -4,10 +4,10 @@
 //   (2) lambda, d_lambda backward sweeps + outer products                             (:85-104, :115-134)
 // Step (1) is the fused solve kernel of lqr_api.hip, step (2) is costate_kernel.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
 #include "../../include/dmpc.h"
 #include "api_util.hpp"
+#include "knobs.hpp"
 #include "costate_dma_kernel.hpp"
 #include "costate_wide_kernel.hpp"
 #include "costate_kernels.hpp"
@@ -50,14 +50,10 @@ __global__ __launch_bounds__(256) void concat_tau_kernel(size_t n_rows, int nx, 
 #define DMPC_COSTATE_CONTAINERS(X) X(3, 1) X(4, 4) X(8, 2) X(5, 5) X(8, 4) X(14, 1) X(13, 2) X(12, 3) X(11, 4) X(10, 5) X(9, 6) X(8, 7) X(7, 8)
 #endif
 
-static bool costate_dma_disabled() {  // DMPC_NO_COSTATE_DMA=1: register-prefetch co-state kernel (A/B timing, debugging)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_COSTATE_DMA"); return e && e[0] == '1'; }();
-  return off;
-}
 constexpr int kCostateDmaDepth = 4;
 
 bool costate_sums_available(int T, int B, int nx, int nu) {
-  if (B < 4 || B % 4 != 0 || T < 2 || costate_dma_disabled()) return false;
+  if (B < 4 || B % 4 != 0 || T < 2 || knob_on<Knob::DMPC_NO_COSTATE_DMA>()) return false;
 #define X(NX_, NU_, L_) \
   if (nx == NX_ && nu == NU_) return L_ == 16;
   DMPC_COSTATE_SHAPES(X)
@@ -75,7 +71,7 @@ int launch_costate(int nx, int nu, const CostateArgs &a, hipStream_t stream) {
   if (nx == NX_ && nu == NU_) {                                                                             \
     constexpr int GPB = 256 / L_;                                                                           \
     if constexpr (L_ == 16) { /* inputs staged through an LDS-DMA ring (costate_dma_kernel.hpp) */          \
-      if (al && a.B >= 4 && a.B % 4 == 0 && a.T >= 2 && !costate_dma_disabled()) {                                          \
+      if (al && a.B >= 4 && a.B % 4 == 0 && a.T >= 2 && !knob_on<Knob::DMPC_NO_COSTATE_DMA>()) {                             \
         using Lay = CostateDmaLayout<NX_, NU_, kCostateDmaDepth>;                                           \
         const int waves = (a.B + 3) / 4;                                                                    \
         DMPC_LAUNCH_GGL((costate_dma_kernel<NX_, NU_, kCostateDmaDepth>), dim3((waves + 3) / 4), dim3(256), \
@@ -91,8 +87,8 @@ int launch_costate(int nx, int nu, const CostateArgs &a, hipStream_t stream) {
   // 17 to 31 elements of tau, at most 16 states: four trajectories per wavefront with tau in two registers
   // (costate_wide_kernel.hpp; before, a wavefront per trajectory inside the (16,8) container).  DMPC_NO_WIDE=1: that path.
   {
-    static const bool off = [] { const char *e = getenv("DMPC_NO_WIDE"); return e && e[0] == '1'; }();
-    if (!off && al && a.dC_sum == nullptr && a.B >= 4 && a.B % 4 == 0 && a.T >= 2 && !costate_dma_disabled() &&
+    if (!knob_on<Knob::DMPC_NO_WIDE>() && al && a.dC_sum == nullptr && a.B >= 4 && a.B % 4 == 0 && a.T >= 2 &&
+        !knob_on<Knob::DMPC_NO_COSTATE_DMA>() &&
         (size_t)a.B * (nx + nu) * (nx + nu) * 4 < ((size_t)1 << 31)) {
 #define X(NX_, NU_)                                                                                            \
   if (nx == NX_ && nu == NU_) {                                                                                \
@@ -110,9 +106,7 @@ int launch_costate(int nx, int nu, const CostateArgs &a, hipStream_t stream) {
       // the larger ones of those with one - the 16-lane container stores its rows of dC / dF element by element, this kernel
       // stages them: gradient at B = 4096, T = 50 (9,4) 400 -> 295 us, (11,4) 530 -> 309, (13,2) 568 -> 321; below 13
       // elements of tau the container wins ((6,3) 208 against 247 us).  DMPC_COSTATE_WIDE_MIN_NS moves the threshold.
-      static const bool no_pad = [] { const char *e = getenv("DMPC_NO_CONTAINER"); return e && e[0] == '1'; }();
-      static const int min_ns = [] { const char *e = getenv("DMPC_COSTATE_WIDE_MIN_NS"); return e ? atoi(e) : 13; }();
-      if (!no_pad && nx + nu >= min_ns && nx >= 1 && nu >= 1) {
+      if (!knob_on<Knob::DMPC_NO_CONTAINER>() && nx + nu >= knob_int<Knob::DMPC_COSTATE_WIDE_MIN_NS>() && nx >= 1 && nu >= 1) {
         CostateArgs p = a;
         p.nx_log = nx;
         p.nu_log = nu;
@@ -141,8 +135,7 @@ int launch_costate(int nx, int nu, const CostateArgs &a, hipStream_t stream) {
     }
   }
   {   // a problem without a specialisation padded inside the first container that holds it (the lists of lqr_api.hip)
-    static const bool off = [] { const char *e = getenv("DMPC_NO_CONTAINER"); return e && e[0] == '1'; }();
-    if (!off && a.dC_sum == nullptr) {
+    if (!knob_on<Knob::DMPC_NO_CONTAINER>() && a.dC_sum == nullptr) {
       CostateArgs p = a;
       p.nx_log = nx;
       p.nu_log = nu;
@@ -155,9 +148,8 @@ int launch_costate(int nx, int nu, const CostateArgs &a, hipStream_t stream) {
 #undef X
       {   // wider (17+ states, ragged batches of the wide shapes): a wavefront per trajectory, the step's blocks through an
           // LDS ring at the problem's own dimensions (costate_staged_kernel.hpp); DMPC_NO_STAGED_COSTATE=1: the containers below
-        static const bool staged_off = [] { const char *e = getenv("DMPC_NO_STAGED_COSTATE"); return e && e[0] == '1'; }();
         const size_t shmem = costate_staged_lds_bytes(nx, nu, a.r_cols);
-        if (!staged_off && a.T >= 2 && nx + nu <= 63 && shmem <= 150 * 1024) {
+        if (!knob_on<Knob::DMPC_NO_STAGED_COSTATE>() && a.T >= 2 && nx + nu <= 63 && shmem <= 150 * 1024) {
           if (shmem > 64 * 1024)
             set_max_lds(reinterpret_cast<const void *>(&costate_staged_kernel), (int)shmem);
           DMPC_LAUNCH_GGL(costate_staged_kernel, dim3(a.B), dim3(64), shmem, stream, a, nx, nu);
@@ -214,11 +206,6 @@ size_t dmpc_lqr_kkt_workspace_bytes(int T, int B, int nx, int nu) {
 }
 
 // DiffLqr.backward.  Ks != nullptr: the gains of the forward solve are reused (dmpc_lqr_kkt_grad_saved).
-static bool adjoint_disabled() {  // DMPC_NO_ADJOINT=1: the re-solve + co-state kernels instead of the one-pass gradient (A/B)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_ADJOINT"); return e && e[0] == '1'; }();
-  return off;
-}
-
 static int kkt_grad(int T, int B, int nx, int nu, const float *C, const float *c, const float *F, const float *x,
                     const float *u, const float *Ks, const float *Quu, const float *Qxu, const float *Vv,
                     const float *grad_x, const float *grad_u, int strict_math, float *d_x_init, float *dC, float *dc,
@@ -226,8 +213,8 @@ static int kkt_grad(int T, int B, int nx, int nu, const float *C, const float *c
   if (T <= 1 || B <= 0 || nx <= 0 || nu <= 0) return DMPC_E_BADARG;
   if (!C || !c || !F || !x || !u || !grad_x || !grad_u || !d_x_init || !dc || !ws) return DMPC_E_BADARG;
   if (!aligned16(C) || !aligned16(c) || !aligned16(F) || !aligned16(dC) || !aligned16(dF)) return DMPC_E_BADARG;
-  if (Ks != nullptr && Vv != nullptr && dC != nullptr && dF != nullptr && df != nullptr && !adjoint_disabled() &&
-      aligned16(grad_x) && aligned16(grad_u) && aligned16(Ks) && aligned16(Quu) && aligned16(Qxu) && aligned16(Vv) &&
+  if (Ks != nullptr && Vv != nullptr && dC != nullptr && dF != nullptr && df != nullptr &&
+      !knob_on<Knob::DMPC_NO_ADJOINT>() && aligned16(grad_x) && aligned16(grad_u) && aligned16(Ks) && aligned16(Quu) && aligned16(Qxu) && aligned16(Vv) &&
       aligned16(x) && aligned16(u) && aligned16(dc) && aligned16(df)) {
     // one launch, no C: the affine re-solve whose rollout writes the gradients (lqr_adjoint, lqr_api.hip)
     const int rc1 = lqr_adjoint(T, B, nx, nu, F, grad_x, grad_u, Ks, Quu, Qxu, Vv, x, u, strict_math, d_x_init, dC, dc, dF, df,

@@ -3,10 +3,9 @@
 // LQR_active (mpc/active_constrained_lqr.py:67-202) of the reference.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "../../include/dmpc.h"
 #include "api_util.hpp"
+#include "knobs.hpp"
 #include "lqr_asm_kernel.hpp"
 #include "lqr_dma_kernel.hpp"
 #include "lqr_generic.hpp"
@@ -27,60 +26,40 @@ constexpr size_t kGainLdsBudget = 156 * 1024;   // (round 4: was 64 KB - (8,4) a
 constexpr int kDmaDepthB = DMPC_DMA_DEPTH_B, kDmaDepthF = DMPC_DMA_DEPTH_F;
 constexpr size_t kDmaLdsBudget = 156 * 1024;
 constexpr size_t kAsmLdsBudget = 160 * 1024;
-static bool asm_path_disabled() {  // DMPC_NO_ASM=1 forces the HIP kernels (A/B timing, debugging)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_ASM"); return e && e[0] == '1'; }();
-  return off;
-}
-static bool stash_disabled() {  // DMPC_NO_STASH=1: forward sweep re-reads F by LDS-DMA (A/B timing)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_STASH"); return e && e[0] == '1'; }();
-  return off;
-}
-static bool wave_mfma_disabled() {  // DMPC_NO_WAVE_MFMA=1: large shapes on the readlane HIP kernel (A/B timing)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_WAVE_MFMA"); return e && e[0] == '1'; }();
-  return off;
-}
-static bool container_disabled() {  // DMPC_NO_CONTAINER=1: shapes without a specialisation on the runtime-dimension kernel
-  static const bool off = [] { const char *e = getenv("DMPC_NO_CONTAINER"); return e && e[0] == '1'; }();
-  return off;
-}
-static bool dma_path_disabled() {  // DMPC_NO_DMA=1 forces the register-prefetch kernel (A/B timing, debugging)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_DMA"); return e && e[0] == '1'; }();
-  return off;
-}
-
-// 4 / 3: generated stream with / without the F stash; 6: generated stream, gain rows through the workspace (any horizon);
-// 2: LDS-DMA HIP kernel; 1: register-prefetch HIP kernel; 7: a container (the register-prefetch kernel of a larger shape);
-// 0: runtime-dimension kernel
+// the path (dmpc.h: DMPC_LQR_PATH_*) of a plain solve at a shape with a specialisation of its own
 template <int NX, int NU, int L>
 static int solve_path(int T, int B) {
   if constexpr (L == 16 && LqrAsm<NX, NU, false, false>::kAvailable) {
-    if (B >= 4 && T >= 2 && !asm_path_disabled()) {
+    if (B >= 4 && T >= 2 && !knob_on<Knob::DMPC_NO_ASM>()) {
       if constexpr (LqrAsm<NX, NU, false, true>::kAvailable) {
         if (T <= LqrAsm<NX, NU, false, true>::NSTASH && lqr_asm_lds_bytes<NX, NU, true>(T) <= kAsmLdsBudget &&
-            !stash_disabled())
-          return 4;
+            !knob_on<Knob::DMPC_NO_STASH>())
+          return DMPC_LQR_PATH_ASM_STASH;
       }
-      if (lqr_asm_lds_bytes<NX, NU, false>(T) <= kAsmLdsBudget) return 3;
+      if (lqr_asm_lds_bytes<NX, NU, false>(T) <= kAsmLdsBudget) return DMPC_LQR_PATH_ASM_RING;
       if constexpr (LqrAsm<NX, NU, false, false, false, true>::kAvailable) {
-        if (lqr_asm_lds_bytes<NX, NU, false, false, true>(T) <= kAsmLdsBudget) return 6;
+        if (lqr_asm_lds_bytes<NX, NU, false, false, true>(T) <= kAsmLdsBudget) return DMPC_LQR_PATH_ASM_WS;
       }
     }
   }
   if constexpr (L == 16) {
     using Lay = LqrDmaLayout<NX, NU, kDmaDepthB, kDmaDepthF>;
-    if (B >= 4 && T >= 2 && Lay::lds_bytes(T) <= kDmaLdsBudget && !dma_path_disabled()) return 2;
+    if (B >= 4 && T >= 2 && Lay::lds_bytes(T) <= kDmaLdsBudget && !knob_on<Knob::DMPC_NO_DMA>()) return DMPC_LQR_PATH_DMA;
   }
   if constexpr (L == 64 && NX % 4 == 0 && NU % 4 == 0) {
-    if (!wave_mfma_disabled()) return 5;
+    if (!knob_on<Knob::DMPC_NO_WAVE_MFMA>()) return DMPC_LQR_PATH_WAVE_MFMA;
   }
-  return 1;
+  return DMPC_LQR_PATH_PREFETCH;
 }
+// the generated stream with its gain rows in LDS, with or without the F stash
+static bool asm_lds_path(int path) { return path == DMPC_LQR_PATH_ASM_RING || path == DMPC_LQR_PATH_ASM_STASH; }
 
 // the saving solve: the stash form of the generated stream with room in LDS for the staging area of the saved blocks
 template <int NX, int NU, int L>
 static int saving_available(int T, int B) {
   if constexpr (L == 16 && LqrAsm<NX, NU, true, true, false, false, true>::kAvailable)
-    return solve_path<NX, NU, L>(T, B) == 4 && lqr_asm_lds_bytes<NX, NU, true, true>(T) <= kAsmLdsBudget;
+    return solve_path<NX, NU, L>(T, B) == DMPC_LQR_PATH_ASM_STASH &&
+           lqr_asm_lds_bytes<NX, NU, true, true>(T) <= kAsmLdsBudget;
   return 0;
 }
 
@@ -96,14 +75,14 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
     // c in two arrays / x_init = 0: forms only the generated streams take (lqr_second_solve below)
     bool ok = false;
     if constexpr (L == 16 && LqrAsm<NX, NU, false, false>::kAvailable)
-      ok = mode == kSolve && !masked && a.Ks == nullptr && (solve_path<NX, NU, L>(a.T, a.B) == 3 || solve_path<NX, NU, L>(a.T, a.B) == 4);
+      ok = mode == kSolve && !masked && a.Ks == nullptr && asm_lds_path(solve_path<NX, NU, L>(a.T, a.B));
     if (!ok) return DMPC_E_UNSUPPORTED;
   }
   if (a.Vv_in != nullptr) {
     // DiffLqr.backward in one launch (lqr_adjoint below): the affine re-solve whose rollout writes the gradients
     if constexpr (L == 16 && LqrAsm<NX, NU, false, true, false, false, false, true, true>::kAvailable) {
       if (mode == kSolve && !masked && a.f == nullptr && a.Ks == nullptr && a.Ks_in != nullptr &&
-          solve_path<NX, NU, L>(a.T, a.B) == 4) {
+          solve_path<NX, NU, L>(a.T, a.B) == DMPC_LQR_PATH_ASM_STASH) {
         const int waves = (a.B + 3) / 4;
         const size_t shmem = lqr_asm_lds_bytes<NX, NU, true>(a.T);
         DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, false, true, false, false, false, true, true>), dim3((waves + 3) / 4),
@@ -116,7 +95,8 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
   if (a.Ks_in != nullptr) {
     // the re-solve from saved gains (dmpc_lqr_saved_solve): the affine form of the generated stream, F in the stash
     if constexpr (L == 16 && LqrAsm<NX, NU, false, true, false, false, false, true>::kAvailable) {
-      if (mode == kSolve && !masked && a.f == nullptr && a.Ks == nullptr && solve_path<NX, NU, L>(a.T, a.B) == 4) {
+      if (mode == kSolve && !masked && a.f == nullptr && a.Ks == nullptr &&
+          solve_path<NX, NU, L>(a.T, a.B) == DMPC_LQR_PATH_ASM_STASH) {
         const int waves = (a.B + 3) / 4;
         const size_t shmem = lqr_asm_lds_bytes<NX, NU, true>(a.T);
         DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, false, true, false, false, false, true>), dim3((waves + 3) / 4),
@@ -129,12 +109,11 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
   if constexpr (L == 16 && LqrAsm<NX, NU, false, false>::kAvailable) {
     // fastest path: the whole solve as one generated instruction stream (lqr_asm_kernel.hpp); with the F stash
     // (no second read of F) when the horizon fits the stash registers
+    const int path = solve_path<NX, NU, L>(a.T, a.B);
     if constexpr (LqrAsm<NX, NU, false, false, true>::kAvailable) {
       // LQR_active on the generated stream: same paths, flags fetched as dwords (B * nu must be a multiple of 4)
-      const int mpath = (mode == kSolve && masked && a.Ks == nullptr && (a.B * NU) % 4 == 0 &&
-                         (reinterpret_cast<uintptr_t>(a.mask) & 3u) == 0)
-                            ? solve_path<NX, NU, L>(a.T, a.B) : 0;
-      if (mpath == 3 || mpath == 4) {
+      if (mode == kSolve && masked && a.Ks == nullptr && (a.B * NU) % 4 == 0 && (reinterpret_cast<uintptr_t>(a.mask) & 3u) == 0 &&
+          asm_lds_path(path)) {
         const int waves = (a.B + 3) / 4;
         const dim3 g((waves + 3) / 4);
         const bool has_f = a.f != nullptr;
@@ -146,14 +125,13 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
     return (int)hipGetLastError();                                                                                      \
   } while (0)
         if constexpr (LqrAsm<NX, NU, false, true, true>::kAvailable) {
-          if (mpath == 4) DMPC_ASM_LAUNCH_M(true);
+          if (path == DMPC_LQR_PATH_ASM_STASH) DMPC_ASM_LAUNCH_M(true);
         }
         DMPC_ASM_LAUNCH_M(false);
 #undef DMPC_ASM_LAUNCH_M
       }
     }
-    if (mode == kBackwardOnly && !masked && solve_path<NX, NU, L>(a.T, a.B) >= 3 && solve_path<NX, NU, L>(a.T, a.B) != 6 &&
-        lqr_asm_lds_bytes<NX, NU, false>(a.T) <= kAsmLdsBudget) {
+    if (mode == kBackwardOnly && !masked && asm_lds_path(path) && lqr_asm_lds_bytes<NX, NU, false>(a.T) <= kAsmLdsBudget) {
       // LqrRecursion.backward(): the generated stream's backward sweep with the gains written to HBM (x == nullptr)
       const int waves = (a.B + 3) / 4;
       const size_t shmem = lqr_asm_lds_bytes<NX, NU, false>(a.T);
@@ -163,11 +141,11 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
         DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, true, false>), dim3((waves + 3) / 4), block, shmem, stream, a);
       return (int)hipGetLastError();
     }
-    const int path = (mode == kSolve && !masked) ? solve_path<NX, NU, L>(a.T, a.B) : 0;
+    const bool plain = mode == kSolve && !masked;
     if constexpr (LqrAsm<NX, NU, false, false, false, true>::kAvailable) {
       // long horizons: the gain rows pass through the workspace instead of LDS (the caller's Ks / ks are another layout:
       // a solve that wants them goes to the kernels below)
-      if (path == 6 && a.Ks == nullptr && a.wsK != nullptr && a.c_u == nullptr && a.x_init != nullptr) {
+      if (plain && path == DMPC_LQR_PATH_ASM_WS && a.Ks == nullptr && a.wsK != nullptr && a.c_u == nullptr && a.x_init != nullptr) {
         const int waves = (a.B + 3) / 4;
         const size_t shmem = lqr_asm_lds_bytes<NX, NU, false, false, true>(a.T);
         if (a.f != nullptr) DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, true, false, false, false, true>), dim3((waves + 3) / 4), block, shmem, stream, a);
@@ -175,7 +153,7 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
         return (int)hipGetLastError();
       }
     }
-    if (path >= 3 && path != 6) {
+    if (plain && asm_lds_path(path)) {
       const int waves = (a.B + 3) / 4;
       const dim3 g((waves + 3) / 4);
       const bool has_f = a.f != nullptr, write_k = a.Ks != nullptr;
@@ -199,7 +177,7 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
     return (int)hipGetLastError();                                                                               \
   } while (0)
       if constexpr (LqrAsm<NX, NU, false, true>::kAvailable) {
-        if (path == 4) DMPC_ASM_LAUNCH(true);
+        if (path == DMPC_LQR_PATH_ASM_STASH) DMPC_ASM_LAUNCH(true);
       }
       DMPC_ASM_LAUNCH(false);
 #undef DMPC_ASM_LAUNCH
@@ -208,7 +186,7 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
   if constexpr (L == 64 && NX % 4 == 0 && NU % 4 == 0) {
     // large shapes: backward sweep on the matrix cores (lqr_wave_mfma.hpp, its own translation unit; plain and
     // LQR_active), gains through HBM, then the bandwidth-bound forward-only kernel
-    if (mode != kForwardOnly && !wave_mfma_disabled()) {
+    if (mode != kForwardOnly && !knob_on<Knob::DMPC_NO_WAVE_MFMA>()) {
       LqrArgs s = a;
       if (s.Ks == nullptr && s.wsK == nullptr) return DMPC_E_WORKSPACE;
       // solve_recursion: the wavefront that finished a trajectory's backward sweep rolls it out in the same launch
@@ -220,7 +198,7 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
     // trajectories, gains + rings within the 160 KB of a CU
     using Lay = LqrDmaLayout<NX, NU, kDmaDepthB, kDmaDepthF>;
     if (mode == kSolve && !masked && a.B >= 4 && a.T >= 2 && Lay::lds_bytes(a.T) <= kDmaLdsBudget &&
-        !dma_path_disabled()) {
+        !knob_on<Knob::DMPC_NO_DMA>()) {
       const int waves = (a.B + 3) / 4;
       DMPC_LAUNCH_GGL((lqr_dma_kernel<NX, NU, kDmaDepthB, kDmaDepthF>), dim3((waves + 3) / 4), block,
                          Lay::lds_bytes(a.T), stream, a);
@@ -239,7 +217,7 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
         // LDS ((8,4) T = 50: 96 against 84 us - hence only here), level at T = 100, ahead at T = 200 ((4,4): 221 against 267 us)
         using LayK = LqrDmaLayout<NX, NU, kDmaDepthB, kDmaDepthF, true>;
         if (!masked && a.B >= 4 && a.T >= 2 && a.wsK != nullptr && a.Ks == nullptr && LayK::lds_bytes(a.T) <= kDmaLdsBudget &&
-            !dma_path_disabled()) {
+            !knob_on<Knob::DMPC_NO_DMA>()) {
           const int waves = (a.B + 3) / 4;
           DMPC_LAUNCH_GGL((lqr_dma_kernel<NX, NU, kDmaDepthB, kDmaDepthF, true>), dim3((waves + 3) / 4), block,
                              LayK::lds_bytes(a.T), stream, a);
@@ -263,9 +241,16 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
   return (int)hipGetLastError();
 }
 
+// quick single-shape builds for kernel experiments (scripts/*variants.sh): no containers, and no wide kernels unless
+// DMPC_EXPERIMENT_WITH_WIDE
+#if defined(DMPC_EXPERIMENT_ONLY_32_8) || defined(DMPC_EXPERIMENT_ONLY_8_2) || defined(DMPC_EXPERIMENT_ONLY_4_4) || \
+    defined(DMPC_EXPERIMENT_ONLY_8_4)
+#define DMPC_EXPERIMENT_ONE_SHAPE
+#endif
+
 // The shapes with a register-resident specialisation.  Anything else (ns + 1 <= 64) goes to the
 // runtime-dimension LDS kernel in lqr_generic.hpp.
-#if defined(DMPC_EXPERIMENT_ONLY_32_8)  // quick single-shape builds for kernel experiments (scripts/*variants.sh)
+#if defined(DMPC_EXPERIMENT_ONLY_32_8)
 #define DMPC_LQR_SHAPES(X) X(32, 8, 64)
 #elif defined(DMPC_EXPERIMENT_ONLY_8_2)
 #define DMPC_LQR_SHAPES(X) X(8, 2, 16)
@@ -282,8 +267,7 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
 // Containers: register-resident kernels that also take any SMALLER problem (lqr_kernel<..., PAD>; the loads pad it in
 // place), in the order they are tried - fewest columns first, fewest controls among equals.  Every shape with
 // nx + nu <= 15 and nu <= 8 has one.
-#if defined(DMPC_EXPERIMENT_ONLY_32_8) || defined(DMPC_EXPERIMENT_ONLY_8_2) || defined(DMPC_EXPERIMENT_ONLY_4_4) || \
-    defined(DMPC_EXPERIMENT_ONLY_8_4)
+#ifdef DMPC_EXPERIMENT_ONE_SHAPE
 #define DMPC_LQR_CONTAINERS(X)
 #else
 // (round 4: five to eight controls too - the gain solve on the rows needs no NU x NU LU per lane; before, (5,5) ran a
@@ -292,8 +276,7 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
 #endif
 
 // ... and the wavefront-per-trajectory kernels take what is larger, up to 32 states and 8 controls
-#if defined(DMPC_EXPERIMENT_ONLY_32_8) || defined(DMPC_EXPERIMENT_ONLY_8_2) || defined(DMPC_EXPERIMENT_ONLY_4_4) || \
-    defined(DMPC_EXPERIMENT_ONLY_8_4)
+#ifdef DMPC_EXPERIMENT_ONE_SHAPE
 #define DMPC_LQR_WAVE_CONTAINERS(X)
 #else
 #define DMPC_LQR_WAVE_CONTAINERS(X) X(16, 8) X(32, 8)
@@ -302,18 +285,13 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
 // 17 to 32 augmented columns with at most 16 states: the wide 16-lane row kernel (lqr_wide_kernel.hpp; two registers per
 // matrix row, four trajectories per wavefront) for the plain fused solve of exactly these shapes - round 4; before, a
 // wavefront per trajectory inside the (16,8) matrix-core instance.  DMPC_NO_WIDE=1: that path (A/B timing).
-#if (defined(DMPC_EXPERIMENT_ONLY_32_8) || defined(DMPC_EXPERIMENT_ONLY_8_2) || defined(DMPC_EXPERIMENT_ONLY_4_4) || \
-     defined(DMPC_EXPERIMENT_ONLY_8_4)) && !defined(DMPC_EXPERIMENT_WITH_WIDE)
+#if defined(DMPC_EXPERIMENT_ONE_SHAPE) && !defined(DMPC_EXPERIMENT_WITH_WIDE)
 #define DMPC_LQR_WIDE_SHAPES(X)
 #else
 #define DMPC_LQR_WIDE_SHAPES(X) X(16, 4) X(16, 8) X(12, 4) X(12, 8)
 /* ((8,4) as a one-register instance of the same kernel - the template takes it - measured 94 us against lqr_kernel's 84: not used) */
 #endif
 #define DMPC_LQR_WIDE_CONTAINERS(X) X(12, 4) X(16, 4) X(12, 8) X(16, 8)   /* fewest columns first */
-static bool wide_disabled() {
-  static const bool off = [] { const char *e = getenv("DMPC_NO_WIDE"); return e && e[0] == '1'; }();
-  return off;
-}
 static bool wide_shape(int nx, int nu) {
 #define X(NX_, NU_) \
   if (nx == NX_ && nu == NU_) return true;
@@ -331,8 +309,10 @@ static bool wide_container_shape(int nx, int nu) {
 // the geometric half of wide_ok - shape, batch, horizon and the 32-bit stride bound - shared with dmpc_lqr_solve_path, so that the
 // path a caller is told (and sizes its workspace for) is the path dispatch_lqr takes
 static bool wide_geometry_ok(int T, int B, int nx, int nu) {
-  const bool exact = wide_shape(nx, nu), padded = wide_container_shape(nx, nu) && B % 4 == 0 && !container_disabled();
-  return (exact || padded) && !wide_disabled() && B >= 4 && T >= 2 && (size_t)B * (nx + nu) * (nx + nu) * 4 < ((size_t)1 << 31);
+  const bool exact = wide_shape(nx, nu);
+  const bool padded = wide_container_shape(nx, nu) && B % 4 == 0 && !knob_on<Knob::DMPC_NO_CONTAINER>();
+  return (exact || padded) && !knob_on<Knob::DMPC_NO_WIDE>() && B >= 4 && T >= 2 &&
+         (size_t)B * (nx + nu) * (nx + nu) * 4 < ((size_t)1 << 31);
 }
 static bool wide_ok(int mode, int nx, int nu, const LqrArgs &a) {
   // (the generated streams' own argument forms - c in two arrays, saved gains, x_init = 0 - are not its business)
@@ -346,16 +326,10 @@ static int launch_lqr_wide(int nx, int nu, const LqrArgs &a, hipStream_t stream)
     constexpr int DB = 2, DF = 2;                                                                          \
     constexpr size_t lds = LqrWideLayout<NX_, NU_, DB, DF>::lds_bytes();                                   \
     static_assert(lds <= 160 * 1024, "rings beyond a CU's LDS");                                           \
-    static const bool attr_once = [] {   /* the LDS request above 64 KB: set once per instantiation, not per launch */ \
-      if (lds > 64 * 1024) {                                                                               \
-        set_max_lds(reinterpret_cast<const void *>(&lqr_wide_kernel<NX_, NU_, DB, DF>), \
-                                  (int)lds);                   \
-        set_max_lds(reinterpret_cast<const void *>(&lqr_wide_kernel<NX_, NU_, DB, DF, false, true>), \
-                                  (int)lds);                   \
-      }                                                                                                    \
-      return true;                                                                                         \
-    }();                                                                                                   \
-    (void)attr_once;                                                                                       \
+    if (lds > 64 * 1024) {                                                                                 \
+      set_max_lds(reinterpret_cast<const void *>(&lqr_wide_kernel<NX_, NU_, DB, DF>), (int)lds);           \
+      set_max_lds(reinterpret_cast<const void *>(&lqr_wide_kernel<NX_, NU_, DB, DF, false, true>), (int)lds); \
+    }                                                                                                      \
     if (a.mask != nullptr) {                                                                               \
       DMPC_LAUNCH_GGL((lqr_wide_kernel<NX_, NU_, DB, DF, false, true>), grid, block, lds, stream, a);      \
     } else {                                                                                               \
@@ -410,7 +384,7 @@ static int launch_lqr_wave_container(int mode, int nx, int nu, const LqrArgs &a0
   if (mode != kForwardOnly) {
     if (a.Ks == nullptr) { a.Ks = a.wsK; a.ks = a.wsk; }
     if (a.Ks == nullptr) return DMPC_E_WORKSPACE;
-    if (!wave_mfma_disabled()) {   // a size that IS one of the instances: the exact kernel (rollout in the same launch)
+    if (!knob_on<Knob::DMPC_NO_WAVE_MFMA>()) {   // a size that IS one of the instances: the exact kernel (rollout in the same launch)
       const int rx = launch_lqr_wave_mfma_backward(nx, nu, masked, mode == kSolve, a, stream);
       if (rx != DMPC_E_UNSUPPORTED) return rx;
     }
@@ -429,12 +403,14 @@ static int launch_lqr_wave_container(int mode, int nx, int nu, const LqrArgs &a0
 
 static int lqr_family(int nx, int nu) {
 #define X(NX_, NU_, L_) \
-  if (nx == NX_ && nu == NU_) return L_ == 16 ? 1 : 2;
+  if (nx == NX_ && nu == NU_) return L_ == 16 ? DMPC_LQR_FAMILY_ROW16 : DMPC_LQR_FAMILY_WAVE;
   DMPC_LQR_SHAPES(X)
 #undef X
-  if (nx >= 1 && nu >= 1 && has_container(nx, nu)) return 4;
-  if (nx >= 1 && nu >= 1 && nx + nu + 1 <= kGenericMaxCols && lqr_generic_lds_bytes(1, nx, nu, false) <= 64 * 1024) return 3;
-  if (nx >= 1 && nu >= 1) return 5;     // any size: a workgroup per trajectory, matrices in the caller's workspace (lqr_tiled.hpp)
+  if (nx >= 1 && nu >= 1 && has_container(nx, nu)) return DMPC_LQR_FAMILY_CONTAINER;
+  if (nx >= 1 && nu >= 1 && nx + nu + 1 <= kGenericMaxCols && lqr_generic_lds_bytes(1, nx, nu, false) <= 64 * 1024)
+    return DMPC_LQR_FAMILY_GENERIC;
+  // any size: a workgroup per trajectory, matrices in the caller's workspace (lqr_tiled.hpp)
+  if (nx >= 1 && nu >= 1) return DMPC_LQR_FAMILY_TILED;
   return DMPC_E_UNSUPPORTED;
 }
 
@@ -481,7 +457,8 @@ static int dispatch_lqr(int mode, int nx, int nu, const LqrArgs &a, hipStream_t 
   if (a.c_u != nullptr || a.Ks_in != nullptr || a.Vv_in != nullptr || a.Quu_out != nullptr ||
       (a.x_init == nullptr && a.x != nullptr))
     return DMPC_E_UNSUPPORTED;
-  if (lqr_family(nx, nu) == 4 && !container_disabled()) {
+  const int family = lqr_family(nx, nu);
+  if (family == DMPC_LQR_FAMILY_CONTAINER && !knob_on<Knob::DMPC_NO_CONTAINER>()) {
 #define X(NX_, NU_) \
   if (nx <= NX_ && nu <= NU_) return launch_lqr_container<NX_, NU_>(mode, nx, nu, a, stream);
     DMPC_LQR_CONTAINERS(X)
@@ -491,7 +468,7 @@ static int dispatch_lqr(int mode, int nx, int nu, const LqrArgs &a, hipStream_t 
     DMPC_LQR_WAVE_CONTAINERS(X)
 #undef X
   }
-  if (lqr_family(nx, nu) == 3 || lqr_family(nx, nu) == 4) {
+  if (family == DMPC_LQR_FAMILY_GENERIC || family == DMPC_LQR_FAMILY_CONTAINER) {
     const int rc = launch_lqr_generic(mode, nx, nu, a, stream);
     if (rc != DMPC_E_UNSUPPORTED) return rc;      // (its matrices did not fit in LDS: the tiled kernel takes any size)
   }
@@ -551,15 +528,17 @@ int dmpc_lqr_kernel_family(int nx, int nu) { return lqr_family(nx, nu); }
 
 int dmpc_lqr_solve_path(int T, int B, int nx, int nu) {
   if (T <= 0 || B <= 0) return DMPC_E_BADARG;
-  if (wide_shape(nx, nu) && wide_geometry_ok(T, B, nx, nu)) return 9;   // lqr_wide_kernel (given the workspace)
+  if (wide_shape(nx, nu) && wide_geometry_ok(T, B, nx, nu)) return DMPC_LQR_PATH_WIDE;   // lqr_wide_kernel (given the workspace)
 #define X(NX_, NU_, L_) \
   if (nx == NX_ && nu == NU_) return solve_path<NX_, NU_, L_>(T, B);
   DMPC_LQR_SHAPES(X)
 #undef X
-  if (wide_container_shape(nx, nu) && wide_geometry_ok(T, B, nx, nu)) return 9;
-  if (lqr_family(nx, nu) == 4 && !container_disabled()) return 7;   // a container kernel (lqr_kernel<..., PAD>)
-  if (lqr_family(nx, nu) == 5) return 8;                              // lqr_tiled_kernel: any size
-  return (lqr_family(nx, nu) == 3 || lqr_family(nx, nu) == 4) ? 0 : DMPC_E_UNSUPPORTED;
+  if (wide_container_shape(nx, nu) && wide_geometry_ok(T, B, nx, nu)) return DMPC_LQR_PATH_WIDE;
+  const int family = lqr_family(nx, nu);
+  if (family == DMPC_LQR_FAMILY_CONTAINER && !knob_on<Knob::DMPC_NO_CONTAINER>()) return DMPC_LQR_PATH_CONTAINER;
+  if (family == DMPC_LQR_FAMILY_TILED) return DMPC_LQR_PATH_TILED;
+  if (family == DMPC_LQR_FAMILY_GENERIC || family == DMPC_LQR_FAMILY_CONTAINER) return DMPC_LQR_PATH_GENERIC;
+  return DMPC_E_UNSUPPORTED;
 }
 
 int dmpc_lqr_saving_available(int T, int B, int nx, int nu) {
@@ -579,13 +558,14 @@ size_t dmpc_lqr_workspace_bytes(int T, int B, int nx, int nu) {
   size_t bytes = (size_t)T * B * nu * (nx + nu + 1 > 12 ? nx + nu + 1 : 12) * sizeof(float);
   // (a shape padded inside an instance of the wide row kernel: gain rows of the INSTANCE's width - at most 8 rows of 25)
   if (wide_container_shape(nx, nu)) bytes = (size_t)T * B * 8 * 25 * sizeof(float);
-  // the shapes beyond a wavefront's 64 columns (family 5) keep the matrices of every trajectory behind the gains
-  if (lqr_family(nx, nu) == 5) bytes = round_up(bytes, 256) + (size_t)B * tiled_scratch_floats(nx, nu) * sizeof(float);
+  // the shapes beyond a wavefront's 64 columns (the tiled family) keep the matrices of every trajectory behind the gains
+  if (lqr_family(nx, nu) == DMPC_LQR_FAMILY_TILED)
+    bytes = round_up(bytes, 256) + (size_t)B * tiled_scratch_floats(nx, nu) * sizeof(float);
   return bytes;
 }
 
 static float *tiled_scratch_of(void *ws, int T, int B, int nx, int nu) {
-  if (ws == nullptr || lqr_family(nx, nu) != 5) return nullptr;
+  if (ws == nullptr || lqr_family(nx, nu) != DMPC_LQR_FAMILY_TILED) return nullptr;
   return reinterpret_cast<float *>(static_cast<char *>(ws) +
                                    round_up((size_t)T * B * nu * (nx + nu + 1 > 12 ? nx + nu + 1 : 12) * sizeof(float), 256));
 }
@@ -630,7 +610,7 @@ int dmpc_lqr_saved_solve(int T, int B, int nx, int nu, const float *c, const flo
   if (T <= 1 || B <= 0 || nx <= 0 || nu <= 0) return DMPC_E_BADARG;
   if (!c || !F || !Ks || !Quu || !Qxu || !x_init || !x_out || !u_out) return DMPC_E_BADARG;
   if (!aligned16(c) || !aligned16(F) || !aligned16(Ks) || !aligned16(Quu) || !aligned16(Qxu)) return DMPC_E_BADARG;
-  if (dmpc_lqr_solve_path(T, B, nx, nu) != 4 || B % 4 != 0) return DMPC_E_UNSUPPORTED;
+  if (dmpc_lqr_solve_path(T, B, nx, nu) != DMPC_LQR_PATH_ASM_STASH || B % 4 != 0) return DMPC_E_UNSUPPORTED;
   LqrArgs a{T, B, nullptr, c, F, nullptr, x_init, nullptr, nullptr, nullptr, nullptr, nullptr, x_out, u_out, info};
   a.Ks_in = Ks;
   a.Quu_in = Quu;

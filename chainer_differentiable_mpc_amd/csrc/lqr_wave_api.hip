@@ -4,18 +4,13 @@
 
 #include "../../include/dmpc.h"
 #include "api_util.hpp"
+#include "knobs.hpp"
 #include "lqr_wave_api.hpp"
 #include "lqr_staged_forward.hpp"
 #include "lqr_wave_mfma.hpp"
 #include "lqr_tile16.hpp"
 
 namespace dmpc {
-
-// DMPC_NO_TILE16=1: the plain sweep on the 4x4x1 outer-product kernel of lqr_wave_mfma.hpp (A/B timing)
-static bool tile16_disabled() {
-  static const bool off = [] { const char *e = getenv("DMPC_NO_TILE16"); return e && e[0] == '1'; }();
-  return off;
-}
 
 // the plain (unclamped) sweep on 16x16x4 tiles (lqr_tile16.hpp); DMPC_E_UNSUPPORTED - nothing launched - for other shapes
 static int launch_lqr_tile16(int nx, int nu, bool rollout, const LqrArgs &a, hipStream_t stream) {
@@ -24,14 +19,8 @@ static int launch_lqr_tile16(int nx, int nu, bool rollout, const LqrArgs &a, hip
   if (nx == NX_ && nu == NU_) {                                                                                       \
     constexpr size_t lds = Tile16Layout<NX_, NU_>::lds_bytes();                                                       \
     static_assert(DMPC_T16_OCC * lds <= 160 * 1024, "DMPC_T16_OCC workgroups per CU");                                                    \
-    static const bool once = [] {                                                                                     \
-      set_max_lds(reinterpret_cast<const void *>(&lqr_tile16_kernel<NX_, NU_, true>), \
-                                (int)lds);                                \
-      set_max_lds(reinterpret_cast<const void *>(&lqr_tile16_kernel<NX_, NU_, false>), \
-                                (int)lds);                                \
-      return true;                                                                                                    \
-    }();                                                                                                              \
-    (void)once;                                                                                                       \
+    set_max_lds(reinterpret_cast<const void *>(&lqr_tile16_kernel<NX_, NU_, true>), (int)lds);                       \
+    set_max_lds(reinterpret_cast<const void *>(&lqr_tile16_kernel<NX_, NU_, false>), (int)lds);                      \
     if (rollout) DMPC_LAUNCH_GGL((lqr_tile16_kernel<NX_, NU_, true>), grid, block, lds, stream, a);                   \
     else DMPC_LAUNCH_GGL((lqr_tile16_kernel<NX_, NU_, false>), grid, block, lds, stream, a);                          \
     return (int)hipGetLastError();                                                                                    \
@@ -44,7 +33,8 @@ static int launch_lqr_tile16(int nx, int nu, bool rollout, const LqrArgs &a, hip
 
 int launch_lqr_wave_mfma_backward(int nx, int nu, bool masked, bool rollout, const LqrArgs &a, hipStream_t stream) {
   const dim3 grid((a.B + 3) / 4), block(256);   // four wavefronts (= trajectories) per workgroup, one per SIMD
-  if (!masked && !tile16_disabled()) {
+  // DMPC_NO_TILE16=1: the plain sweep on the 4x4x1 outer-product kernel of lqr_wave_mfma.hpp (A/B timing)
+  if (!masked && !knob_on<Knob::DMPC_NO_TILE16>()) {
     const int rt = launch_lqr_tile16(nx, nu, rollout, a, stream);
     if (rt != DMPC_E_UNSUPPORTED) return rt;
   }
@@ -112,9 +102,9 @@ int launch_lqr_wave_container_sweep(int cnx, int cnu, bool masked, const LqrArgs
 // the rollout of a problem padded inside those instances (gains from a.Ks / a.ks, else the workspace), inputs staged through LDS
 // (lqr_staged_forward.hpp).  DMPC_E_UNSUPPORTED - nothing launched - for the clamped rollout, T == 1 or DMPC_NO_STAGED_FWD=1.
 int launch_lqr_staged_forward(int nx, int nu, const LqrArgs &a, hipStream_t stream) {
-  static const bool off = [] { const char *e = getenv("DMPC_NO_STAGED_FWD"); return e && e[0] == '1'; }();
   const size_t shmem = lqr_staged_fwd_lds_bytes(nx, nu);
-  if (off || a.mask != nullptr || a.T < 2 || nx + nu > 63 || shmem > 150 * 1024 || (a.Ks == nullptr && a.wsK == nullptr))
+  if (knob_on<Knob::DMPC_NO_STAGED_FWD>() || a.mask != nullptr || a.T < 2 || nx + nu > 63 || shmem > 150 * 1024 ||
+      (a.Ks == nullptr && a.wsK == nullptr))
     return DMPC_E_UNSUPPORTED;
   if (shmem > 64 * 1024)
     set_max_lds(reinterpret_cast<const void *>(&lqr_staged_forward_kernel), (int)shmem);

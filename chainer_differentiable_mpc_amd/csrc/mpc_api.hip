@@ -2,12 +2,12 @@
 // (include/dmpc.h sections C and E).  Replaces PNQP (mpc/pnqp.py:37-201), MPCstep.forward /
 // backward_rec / forward_rec / backward (mpc/mpc_step.py:70-460) of the reference.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 
 #include <algorithm>
 
 #include "../../include/dmpc.h"
 #include "api_util.hpp"
+#include "knobs.hpp"
 #include "costate_args.hpp"
 #include "box_ddp_kernels.hpp"
 #include "mpc_asm_kernel.hpp"
@@ -98,22 +98,12 @@ static int launch_cooperative(const void *kernel, dim3 grid, dim3 block, void **
   return (int)e;
 }
 
-// DMPC_NO_COOP_REGISTER=1 (read at every call: tests switch it): batch-coupled problems skip the register kernels'
-// whole-batch-resident launch and run on mpc_coupled.hpp's fixed grid, as they do when that launch does not fit
-static bool coupled_register_disabled() {
-  const char *e = getenv("DMPC_NO_COOP_REGISTER");
-  return e && e[0] == '1';
-}
-
 // mpc_coupled.hpp's kernels: a grid that is resident whatever the batch - resident_workgroups() of this kernel, at most one per
 // row; halved if the runtime still refuses
 static int launch_fixed_grid(const void *kernel, int rows, void **args, hipStream_t stream) {
   long long cap = resident_workgroups(kernel, kTiledThreads, 0);
   if (cap <= 0) return DMPC_E_UNSUPPORTED;
-  if (const char *e = getenv("DMPC_FIXED_GRID_MAX")) {   // (experiments; read at every call)
-    const long long v = atoll(e);
-    if (v >= 1) cap = v;
-  }
+  if (const long long v = knob_int<Knob::DMPC_FIXED_GRID_MAX>(); v >= 1) cap = v;   // (experiments)
   note_kernel(kernel);
   for (long long g = std::min<long long>(cap, rows); g >= 1; g /= 2) {
     const hipError_t e = hipLaunchCooperativeKernel(kernel, dim3((unsigned)g), dim3(kTiledThreads), args, 0, stream);
@@ -154,34 +144,12 @@ static int launch_mpc_back_fixed_grid(int nx, int nu, const MpcBackArgs &a, hipS
 #else
 #define DMPC_MPC_CONTAINERS(X) X(3, 1) X(4, 4) X(8, 2) X(8, 4) X(14, 1) X(13, 2) X(12, 3) X(11, 4)
 #endif
-static bool mpc_container_disabled() {   // DMPC_NO_CONTAINER=1: the runtime-dimension kernels (A/B timing)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_CONTAINER"); return e && e[0] == '1'; }();
-  return off;
-}
-
-static bool mpc_staged_forward_disabled() {   // DMPC_NO_MPC_STAGED_FWD=1: mpc_generic_forward_kernel (A/B timing, parity between them)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_MPC_STAGED_FWD"); return e && e[0] == '1'; }();
-  return off;
-}
-
 // Which shapes run padded inside the wide row kernels' instances (sweep and line search alike): those without a 16-lane MPC
 // container (16 and more elements of tau, or more than four controls) and, of those with one, three and four controls from
 // 12 elements on - MPCstep.forward at B = 4096, T = 50: (9,4) 707 -> 605 us, (11,4) 769 -> 645, (10,3) 629 -> 578; with one
 // or two controls the container's short QP wins ((13,2) 568 against 695 us, (14,1) 460 against 562).
 static bool mpc_wide_padded(int nx, int nu) { return nx + nu >= 16 || nu > 4 || (nu >= 3 && nx + nu >= 12); }
 
-static bool mpc_wave_disabled() {   // DMPC_NO_MPC_WAVE=1: wide MPC shapes on the runtime-dimension kernel (A/B timing)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_MPC_WAVE"); return e && e[0] == '1'; }();
-  return off;
-}
-static bool mpc_dma_disabled() {
-  static const bool off = [] { const char *e = getenv("DMPC_NO_MPC_DMA"); return e && e[0] == '1'; }();
-  return off;
-}
-static bool mpc_asm_disabled() {
-  static const bool off = [] { const char *e = getenv("DMPC_NO_MPC_ASM"); return e && e[0] == '1'; }();
-  return off;
-}
 template <class... P>
 static bool aligned16(const P *...p) {   // nullptr counts as aligned
   return ((reinterpret_cast<uintptr_t>(p) | ...) & 15u) == 0;
@@ -192,7 +160,7 @@ static int select_parts(int B) { const int n = (B + 255) / 256; return n < 1 ? 1
 
 // can launch_mpc_back stage this problem's inputs through the LDS-DMA ring?
 static bool mpc_back_dma_ok(const MpcBackArgs &a) {
-  return a.sync == nullptr && a.B >= 4 && a.B % 4 == 0 && !mpc_dma_disabled() &&
+  return a.sync == nullptr && a.B >= 4 && a.B % 4 == 0 && !knob_on<Knob::DMPC_NO_MPC_DMA>() &&
          aligned16(a.C, a.c, a.F, a.f, a.controls, a.lower, a.upper, a.states);
 }
 
@@ -205,13 +173,15 @@ static int launch_mpc_back(int nx, int nu, const MpcBackArgs &a_in, hipStream_t 
     if (e != hipSuccess) return (int)e;
   }
   void *args1[] = {&a};
-  const bool coop_off = a.sync != nullptr && coupled_register_disabled();
+  // DMPC_NO_COOP_REGISTER=1: batch-coupled problems skip the register kernels' whole-batch-resident launch and run on
+  // mpc_coupled.hpp's fixed grid, as they do when that launch does not fit
+  const bool coop_off = a.sync != nullptr && knob_on_now<Knob::DMPC_NO_COOP_REGISTER>();
   // per-trajectory termination, whole wavefronts of four trajectories, 16-byte aligned runs: inputs through the LDS-DMA
   // ring of mpc_dma_kernels.hpp (DMPC_NO_MPC_DMA=1: the register-bank kernel, for A/B timing)
   const bool dma_ok = mpc_back_dma_ok(a);
   // The sweep as one generated instruction stream with the box QP inside (mpc_asm_kernel.hpp): shapes the generator
   // covers, c already re-centred, no bookkeeping riding along.  DMPC_NO_MPC_ASM=1: the HIP kernels (A/B timing).
-  if (dma_ok && a.T >= 2 && !mpc_asm_disabled() && (sel == nullptr || sel_sync != nullptr) &&
+  if (dma_ok && a.T >= 2 && !knob_on<Knob::DMPC_NO_MPC_ASM>() && (sel == nullptr || sel_sync != nullptr) &&
       (a.states == nullptr || a.f == nullptr)) {
     const int n_sel = sel != nullptr ? select_parts(a.B) : 0;
     const dim3 grid((a.B + 15) / 16 + n_sel), block(256);
@@ -268,8 +238,7 @@ static int launch_mpc_back(int nx, int nu, const MpcBackArgs &a_in, hipStream_t 
   // trajectories per wavefront, matrix-core products; before, the runtime-dimension kernel - 2.0 ms at (12,4), B = 4096, T = 50 -
   // and, at (16,8), a wavefront per trajectory).  DMPC_NO_WIDE=1: those.
   {
-    static const bool wide_off = [] { const char *e = getenv("DMPC_NO_WIDE"); return e && e[0] == '1'; }();
-    if (!wide_off && a.sync == nullptr && sel == nullptr && a.B >= 4 && a.T >= 2 &&
+    if (!knob_on<Knob::DMPC_NO_WIDE>() && a.sync == nullptr && sel == nullptr && a.B >= 4 && a.T >= 2 &&
         aligned16(a.C, a.c, a.F, a.f) && (size_t)a.B * (nx + nu) * (nx + nu) * 4 < ((size_t)1 << 31)) {
       LqrArgs s{a.T, a.B, a.C, a.c, a.F, a.f, nullptr, nullptr, a.Ks, a.ks, nullptr, nullptr, nullptr, nullptr, a.info};
       s.mpc_controls = a.controls;
@@ -293,7 +262,8 @@ static int launch_mpc_back(int nx, int nu, const MpcBackArgs &a_in, hipStream_t 
 #undef X
       // ... and padded inside the smallest of those instances: every other shape with at most 16 states, 8 controls and
       // no 16-lane container (nx + nu >= 16, or more than four controls: (5,5) 2.0 -> 1.3 ms per MPCstep.forward), whole wavefronts
-      if (nx >= 1 && nu >= 1 && nx <= 16 && nu <= 8 && mpc_wide_padded(nx, nu) && a.B % 4 == 0 && !mpc_container_disabled()) {
+      if (nx >= 1 && nu >= 1 && nx <= 16 && nu <= 8 && mpc_wide_padded(nx, nu) && a.B % 4 == 0 &&
+          !knob_on<Knob::DMPC_NO_CONTAINER>()) {
         s.nx_log = nx;
         s.nu_log = nu;
 #define X(NX_, NU_)                                                                                            \
@@ -313,7 +283,7 @@ static int launch_mpc_back(int nx, int nu, const MpcBackArgs &a_in, hipStream_t 
   // (16,8), (32,8): the matrix-core sweep with the box QP inside (lqr_wave_mfma_backward<..., MPC>); per-trajectory
   // termination, not inside the device-driven BoxDDP loop (no `done` flag there)
   if (a.sync == nullptr && a.done == nullptr && !a.info_store && ((nx == 16 && nu == 8) || (nx == 32 && nu == 8)) &&
-      a.T >= 1 && !mpc_wave_disabled()) {
+      a.T >= 1 && !knob_on<Knob::DMPC_NO_MPC_WAVE>()) {
     LqrArgs s{a.T, a.B, a.C, a.c, a.F, a.f, nullptr, nullptr, a.Ks, a.ks, nullptr, nullptr, nullptr, nullptr, a.info};
     s.mpc_controls = a.controls;
     s.mpc_lower = a.lower;
@@ -335,9 +305,10 @@ static int launch_mpc_back(int nx, int nu, const MpcBackArgs &a_in, hipStream_t 
     s.nu_log = nu;
     return launch_mpc_wave_container_backward(cnx, cnu, s, stream);
   };
-  const bool wave_ok = a.sync == nullptr && a.done == nullptr && !a.info_store && !mpc_wave_disabled() && !mpc_container_disabled();
+  const bool wave_ok = a.sync == nullptr && a.done == nullptr && !a.info_store && !knob_on<Knob::DMPC_NO_MPC_WAVE>() &&
+                       !knob_on<Knob::DMPC_NO_CONTAINER>();
   const bool small = nu <= 4 && nx + nu <= 15;     // (the 16-lane containers below take these)
-  if (!mpc_container_disabled()) {   // a smaller problem inside the first container that holds it
+  if (!knob_on<Knob::DMPC_NO_CONTAINER>()) {   // a smaller problem inside the first container that holds it
     a.nx_log = nx;
     a.nu_log = nu;
 #define X(NX_, NU_)                                                                                           \
@@ -398,41 +369,27 @@ static int launch_mpc_back(int nx, int nu, const MpcBackArgs &a_in, hipStream_t 
 // shapes that only the tiled kernels take
 static bool mpc_needs_tiles(int nx, int nu) { return !(nx + nu + 1 <= 64 && nu <= kMpcGenericMaxNu); }
 
-static bool spec_line_search_disabled() {  // DMPC_NO_SPEC_LS=1: sequential line search for the pendulum (A/B timing)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_SPEC_LS"); return e && e[0] == '1'; }();
-  return off;
-}
-
-static bool spec4_disabled_early() {  // (DMPC_NO_SPEC4 also selects the lane-per-trajectory rollout)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_SPEC4"); return e && e[0] == '1'; }();
-  return off;
-}
 // rollout + linearisation of the built-in pendulum: four lanes per trajectory when the 16-byte row accesses are aligned
 static void launch_pendulum_rollout(const PendulumArgs &pa, hipStream_t stream) {
-  if (aligned16(pa.F, pa.C) && !spec4_disabled_early())
+  if (aligned16(pa.F, pa.C) && !knob_on<Knob::DMPC_NO_SPEC4>())
     DMPC_LAUNCH_GGL(pendulum_rollout_linearize4_kernel, dim3((4 * pa.B + 255) / 256), dim3(256), 0, stream, pa);
   else
     DMPC_LAUNCH_GGL(pendulum_rollout_linearize_kernel, dim3((pa.B + 63) / 64), dim3(64), 0, stream, pa);
 }
 
-static bool spec4_disabled() {  // DMPC_NO_SPEC4=1: the lane-per-candidate speculative search (A/B timing, longer horizons' path)
-  static const bool off = [] { const char *e = getenv("DMPC_NO_SPEC4"); return e && e[0] == '1'; }();
-  return off;
-}
-
 static int launch_mpc_fwd(int nx, int nu, const MpcFwdArgs &a_in, hipStream_t stream) {
   MpcFwdArgs a = a_in;
-  if (a.dyn_kind == 1 && nx == 3 && nu == 1 && !spec_line_search_disabled()) {
+  if (a.dyn_kind == 1 && nx == 3 && nu == 1 && !knob_on<Knob::DMPC_NO_SPEC_LS>()) {
     // the pendulum's line search usually walks ten or more step sizes: 16 candidates per trajectory at once; every
     // candidate keeps its trajectory in LDS (T * 4 KB per workgroup) when that fits
-    if (a.T <= kSpec4MaxT && !spec4_disabled()) {   // a wavefront per trajectory, all inputs and candidates in LDS
+    if (a.T <= kSpec4MaxT && !knob_on<Knob::DMPC_NO_SPEC4>()) {   // a wavefront per trajectory, all inputs and candidates in LDS
       DMPC_LAUNCH_GGL(mpc_forward_rec_pendulum_spec4_kernel, dim3((a.B + 3) / 4), dim3(256),
                          Spec4Layout::lds_bytes(a.T), stream, a);
       return (int)hipGetLastError();
     }
     const size_t lds = (size_t)a.T * 4 * 256 * sizeof(float);
     a.traj_in_lds = lds <= 96 * 1024 ? 1 : 0;
-    const bool dma = a.B >= 4 && a.B % 4 == 0 && !mpc_dma_disabled() &&
+    const bool dma = a.B >= 4 && a.B % 4 == 0 && !knob_on<Knob::DMPC_NO_MPC_DMA>() &&
                      aligned16(a.C, a.c, a.Ks, a.ks, a.controls, a.lower, a.upper, a.states);
     if (dma)
       DMPC_LAUNCH_GGL(mpc_forward_rec_pendulum_spec_kernel<true>, dim3((a.B + 15) / 16), dim3(256),
@@ -443,10 +400,10 @@ static int launch_mpc_fwd(int nx, int nu, const MpcFwdArgs &a_in, hipStream_t st
     return (int)hipGetLastError();
   }
   // LinDx, whole wavefronts of four trajectories, 16-byte aligned runs: inputs through the LDS-DMA ring
-  const bool fwd_dma = a.dyn_kind == 0 && a.B >= 4 && a.B % 4 == 0 && !mpc_dma_disabled() &&
+  const bool fwd_dma = a.dyn_kind == 0 && a.B >= 4 && a.B % 4 == 0 && !knob_on<Knob::DMPC_NO_MPC_DMA>() &&
                        aligned16(a.C, a.c, a.F, a.f, a.Ks, a.ks, a.controls, a.lower, a.upper, a.states);
   // the line search as one generated instruction stream (mpc_fwd_asm_kernel.hpp); DMPC_NO_MPC_ASM=1: the HIP kernels
-  if (fwd_dma && a.ls_cap > 0 && !mpc_asm_disabled()) {
+  if (fwd_dma && a.ls_cap > 0 && !knob_on<Knob::DMPC_NO_MPC_ASM>()) {
     const dim3 grid((a.B + 15) / 16), block(256);
 #define A(NX_, NU_)                                                                                          \
   if (nx == NX_ && nu == NU_) {                                                                              \
@@ -475,8 +432,7 @@ static int launch_mpc_fwd(int nx, int nu, const MpcFwdArgs &a_in, hipStream_t st
   // 17 to 31 elements of tau, at most 16 states: the line search of the wide row layout (mpc_wide_forward_kernel.hpp: four
   // trajectories per wavefront; before, the runtime-dimension kernel - 0.68 ms at (12,4)).  DMPC_NO_WIDE=1: that one.
   {
-    static const bool wide_off = [] { const char *e = getenv("DMPC_NO_WIDE"); return e && e[0] == '1'; }();
-    if (!wide_off && a.dyn_kind == 0 && a.ls_cap > 0 && a.B >= 4 && a.T >= 2 && a.info_in == nullptr &&
+    if (!knob_on<Knob::DMPC_NO_WIDE>() && a.dyn_kind == 0 && a.ls_cap > 0 && a.B >= 4 && a.T >= 2 && a.info_in == nullptr &&
         aligned16(a.C, a.c, a.F, a.f, a.Ks, a.ks, a.controls, a.lower, a.upper, a.states) &&
         (size_t)a.B * (nx + nu) * (nx + nu) * 4 < ((size_t)1 << 31)) {
 #define X(NX_, NU_)                                                                                            \
@@ -491,7 +447,8 @@ static int launch_mpc_fwd(int nx, int nu, const MpcFwdArgs &a_in, hipStream_t st
   }
       X(12, 4) X(16, 4) X(12, 8) X(16, 8)
 #undef X
-      if (nx >= 1 && nu >= 1 && nx <= 16 && nu <= 8 && mpc_wide_padded(nx, nu) && a.B % 4 == 0 && !mpc_container_disabled()) {
+      if (nx >= 1 && nu >= 1 && nx <= 16 && nu <= 8 && mpc_wide_padded(nx, nu) && a.B % 4 == 0 &&
+          !knob_on<Knob::DMPC_NO_CONTAINER>()) {
         MpcFwdArgs p = a;     // ... and padded inside the smallest of those instances (as the sweep)
         p.nx_log = nx;
         p.nu_log = nu;
@@ -509,7 +466,7 @@ static int launch_mpc_fwd(int nx, int nu, const MpcFwdArgs &a_in, hipStream_t st
       }
     }
   }
-  if (a.dyn_kind == 0 && !mpc_container_disabled()) {
+  if (a.dyn_kind == 0 && !knob_on<Knob::DMPC_NO_CONTAINER>()) {
     a.nx_log = nx;
     a.nu_log = nu;
 #define X(NX_, NU_)                                                                                              \
@@ -520,7 +477,7 @@ static int launch_mpc_fwd(int nx, int nu, const MpcFwdArgs &a_in, hipStream_t st
     DMPC_MPC_CONTAINERS(X)
 #undef X
   }
-  if (a.dyn_kind == 0 && nx + nu + 1 <= 64 && nu <= kMpcGenericMaxNu && !mpc_staged_forward_disabled()) {
+  if (a.dyn_kind == 0 && nx + nu + 1 <= 64 && nu <= kMpcGenericMaxNu && !knob_on<Knob::DMPC_NO_MPC_STAGED_FWD>()) {
     // the inputs of a step through an LDS ring (mpc_staged_forward_kernel); DMPC_NO_MPC_STAGED_FWD=1: the kernel below
     const size_t shmem = mpc_staged_fwd_lds_bytes(nx, nu);
     if (shmem <= 150 * 1024) {
@@ -551,8 +508,8 @@ constexpr int kSyncQpIterMax = 64;   // the workspace queries do not know n_qp_i
 // Both generated streams in one launch (mpc_step_fused_kernel.hpp) when each of them would have been chosen on its own:
 // the conditions of launch_mpc_back's and launch_mpc_fwd's stream branches.  DMPC_NO_MPC_FUSED=1: two launches (A/B).
 static int launch_mpc_step_fused(int nx, int nu, const MpcBackArgs &ba, const MpcFwdArgs &fa, hipStream_t stream) {
-  static const bool off = [] { const char *e = getenv("DMPC_NO_MPC_FUSED"); return e && e[0] == '1'; }();
-  if (off || mpc_asm_disabled() || !mpc_back_dma_ok(ba) || ba.T < 2 || !(ba.states == nullptr || ba.f == nullptr))
+  if (knob_on<Knob::DMPC_NO_MPC_FUSED>() || knob_on<Knob::DMPC_NO_MPC_ASM>() || !mpc_back_dma_ok(ba) || ba.T < 2 ||
+      !(ba.states == nullptr || ba.f == nullptr))
     return DMPC_E_UNSUPPORTED;
   if (!(fa.dyn_kind == 0 && fa.ls_cap > 0 &&
         aligned16(fa.C, fa.c, fa.F, fa.f, fa.Ks, fa.ks, fa.controls, fa.lower, fa.upper, fa.states)))
@@ -720,7 +677,7 @@ int dmpc_pnqp(int B, int n, const float *H, const float *q, const float *lower, 
 #define CASE(N)                                                                                                  \
   case N:                                                                                                        \
     if (sync != nullptr) {                                                                                       \
-      const int rc = coupled_register_disabled()                                                                 \
+      const int rc = knob_on_now<Knob::DMPC_NO_COOP_REGISTER>()                                                  \
                          ? DMPC_E_UNSUPPORTED                                                                    \
                          : launch_cooperative(reinterpret_cast<const void *>(&pnqp_kernel<N>), grid, block, args, 0, stream); \
       return rc == DMPC_E_UNSUPPORTED ? fixed_grid() : rc;                                                       \
@@ -914,7 +871,7 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   // Pendulum: the trajectory the line search accepts IS the next iteration's nominal one, and the search writes its
   // linearisation and re-centred cost while it writes the trajectory - the rollout + linearisation kernel runs for
   // the first iteration only, the nominal states ping-pong between the two state buffers.
-  const bool fuse_lin = dyn_kind == 1 && !spec_line_search_disabled();
+  const bool fuse_lin = dyn_kind == 1 && !knob_on<Knob::DMPC_NO_SPEC_LS>();
   float *x_buf[2] = {xs, x_new};
   const bool copy_here = B <= kDdpCopyHereMaxB && rows * (size_t)(nx + nu) <= kDdpCopyHereMaxElems;
   bool fused_select = false;   // decided at the first sweep: the bookkeeping of iteration i rides in sweep i + 1's launch
@@ -929,9 +886,8 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   if (fuse_lin && nx == 3 && nu == 1 && copy_here) {   // (decided before the first launch: the first iteration's launch also rolls out)
     const MpcBackArgs ba0{T, B, C, c_back, F_hat, nullptr, u_init, u_lower, u_upper, n_qp_iter_max, Ks, ks, ip(w.nqp), info, done,
                           batch_coupled ? reinterpret_cast<unsigned *>(base + w.sync) : nullptr, nullptr, 0};
-    const char *e = getenv("DMPC_NO_DDP_ITER_FUSED");
-    iter_fused = mpc_back_dma_ok(ba0) && T >= 2 && T <= kSpec4MaxT && !spec4_disabled() && !mpc_asm_disabled() &&
-                 aligned16(fp(w.F)) && !(e && e[0] == '1');
+    iter_fused = mpc_back_dma_ok(ba0) && T >= 2 && T <= kSpec4MaxT && !knob_on<Knob::DMPC_NO_SPEC4>() &&
+                 !knob_on<Knob::DMPC_NO_MPC_ASM>() && aligned16(fp(w.F)) && !knob_on_now<Knob::DMPC_NO_DDP_ITER_FUSED>();
   }
   float *u_buf3[3] = {fp(w.u_a), fp(w.u_b), fp(w.u_c)};
   float *u1_2[2] = {u1, fp(w.u1_b)}, *costs_2[2] = {costs, fp(w.costs_b)};

@@ -103,7 +103,7 @@ class LqrRecursion:
         ks = torch.empty((T, B, nu), dtype=torch.float32, device=self._dev)
         info = self._new_info()
         ws, need = None, 0
-        if lib.dmpc_lqr_kernel_family(nx, nu) == 5:     # beyond a wavefront's 64 columns: the sweep's matrices live in a workspace
+        if lib.dmpc_lqr_kernel_family(nx, nu) == _lib.LQR_FAMILY_TILED:   # beyond 64 columns: the sweep's matrices live in a workspace
             need = lib.dmpc_lqr_workspace_bytes(T, B, nx, nu)
             ws = _workspace(need, self._dev)
         with _lib.guard(self._dev):
@@ -249,14 +249,15 @@ def solve_device(C, c, F, f, x_init, mask, T, n_state, n_ctrl, want_gains=False,
     geo = _SOLVE_GEOMETRY.get((T, B, nx, nu))
     if geo is None:       # (three library queries per problem size, not per call)
         geo = _SOLVE_GEOMETRY[(T, B, nx, nu)] = (lib.dmpc_lqr_workspace_bytes(T, B, nx, nu), lib.dmpc_lqr_kernel_family(nx, nu),
-                                                 lib.dmpc_lqr_solve_path(T, B, nx, nu) == 9)
+                                                 lib.dmpc_lqr_solve_path(T, B, nx, nu) == _lib.LQR_PATH_WIDE)
         if len(_SOLVE_GEOMETRY) > 256:
             _SOLVE_GEOMETRY.pop(next(iter(_SOLVE_GEOMETRY)))
     need, family, wide = geo
     per_traj_lds = T * nu * (nx + 1) * 4
-    # (family 5 - beyond 64 columns - keeps every trajectory's matrices in the workspace, whoever receives the gains)
-    # (... and the wide row kernel - solve path 9 - sends its gain rows through it on their way to the rollout)
-    if family == 5 or wide or (not want_gains and (per_traj_lds * 16 > 60 * 1024 or family != 1)):
+    # (the tiled family - beyond 64 columns - keeps every trajectory's matrices in the workspace, whoever receives the gains)
+    # (... and the wide row kernel sends its gain rows through it on their way to the rollout)
+    if family == _lib.LQR_FAMILY_TILED or wide or \
+            (not want_gains and (per_traj_lds * 16 > 60 * 1024 or family != _lib.LQR_FAMILY_ROW16)):
         ws = _workspace(need, dev)
         ws_bytes = need
     with _lib.guard(dev):

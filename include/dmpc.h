@@ -54,28 +54,41 @@ const char *dmpc_source_hash(void);
  * into buf (truncated to buf_bytes) and returns its length; 0 = nothing launched yet.  Diagnostics / benchmark labels. */
 int dmpc_last_kernel_name(char *buf, size_t buf_bytes);
 
-/* Which kernel family a shape dispatches to: 1 = DPP row kernel (16 lanes / trajectory),
- * 2 = wave kernel (64 lanes / trajectory), 3 = generic LDS kernel (runtime dimensions),
- * 4 = a container: the shape has no specialisation of its own and runs padded by the loads inside a larger kernel of
- *     family 1 (nu <= 4, nx + nu <= 15) or 2 (up to 32 states, 8 controls),  <0 unsupported. */
+/* Which kernel family a shape dispatches to (an int; <0 unsupported). */
+enum dmpc_lqr_family_id {
+  DMPC_LQR_FAMILY_ROW16 = 1,     /* DPP row kernel (16 lanes / trajectory) */
+  DMPC_LQR_FAMILY_WAVE = 2,      /* wave kernel (64 lanes / trajectory) */
+  DMPC_LQR_FAMILY_GENERIC = 3,   /* generic LDS kernel (runtime dimensions) */
+  DMPC_LQR_FAMILY_CONTAINER = 4, /* no specialisation of its own: runs padded by the loads inside a larger kernel of family
+                                  * ROW16 (nu <= 4, nx + nu <= 15) or WAVE (up to 32 states, 8 controls) */
+  DMPC_LQR_FAMILY_TILED = 5      /* nx + nu + 1 > 64 (any size): a workgroup per trajectory, matrices in the workspace of
+                                  * dmpc_lqr_workspace_bytes */
+};
 int dmpc_lqr_kernel_family(int nx, int nu);
 
-/* Which kernel a plain (unmasked) dmpc_lqr_solve of this size runs (diagnostics, benchmark labelling):
- *   0 lqr_generic_kernel (runtime dims, LDS)      1 lqr_kernel (HIP, register prefetch)
- *   2 lqr_dma_kernel (HIP, LDS-DMA ring)          3 lqr_asm_kernel, ring (generated stream, F fetched twice)
- *   4 lqr_asm_kernel, stash (generated stream, F kept in accumulation registers)
- *   5 lqr_wave_mfma_backward (one wavefront per trajectory, e.g. (32,8): MFMA backward sweep, then the same wavefront
- *     rolls its trajectory out)
- *   6 lqr_asm_kernel, ring, gain rows through the workspace (horizons whose gain rows do not fit in LDS: T > 74 at
- *     (8,2); needs `ws`)
- *   7 a container: lqr_kernel<..., PAD> of a larger shape, or lqr_wave_mfma_backward<..., PAD> + the forward-only
- *     container kernel (needs `ws` unless the caller takes the gains)
- *   8 lqr_tiled_kernel (any size: a workgroup per trajectory, matrices in `ws`)
- *   9 lqr_wide_kernel (17 to 32 augmented columns, at most 16 states - (16,4), (16,8), (12,4), (12,8), and padded inside
- *     them every shape with nx <= 16, nu <= 8, nx + nu >= 16 when B % 4 == 0: four trajectories per wavefront, two
- *     registers per matrix row, outer products on the matrix cores; plain and masked (LQR_active) solves alike; needs `ws` -
- *     without it, with B < 4, T < 2 or B (nx+nu)^2 floats beyond 2^31 bytes the solve takes path 7 / 5)   <0 unsupported
- *   (round 5: the plain sweep of path 5 at (32,8), (24,8), (32,4), (24,4) is lqr_tile16_kernel - 16x16x4 tiles) */
+/* Which kernel a plain (unmasked) dmpc_lqr_solve of this size runs (an int; <0 unsupported; diagnostics, benchmark
+ * labelling). */
+enum dmpc_lqr_path_id {
+  DMPC_LQR_PATH_GENERIC = 0,   /* lqr_generic_kernel (runtime dims, LDS) */
+  DMPC_LQR_PATH_PREFETCH = 1,  /* lqr_kernel (HIP, register prefetch) */
+  DMPC_LQR_PATH_DMA = 2,       /* lqr_dma_kernel (HIP, LDS-DMA ring) */
+  DMPC_LQR_PATH_ASM_RING = 3,  /* lqr_asm_kernel, ring (generated stream, F fetched twice) */
+  DMPC_LQR_PATH_ASM_STASH = 4, /* lqr_asm_kernel, stash (generated stream, F kept in accumulation registers) */
+  DMPC_LQR_PATH_WAVE_MFMA = 5, /* lqr_wave_mfma_backward (one wavefront per trajectory, e.g. (32,8): MFMA backward sweep,
+                                * then the same wavefront rolls its trajectory out); the plain sweep at (32,8), (24,8),
+                                * (32,4), (24,4) is lqr_tile16_kernel (16x16x4 tiles) */
+  DMPC_LQR_PATH_ASM_WS = 6,    /* lqr_asm_kernel, ring, gain rows through the workspace (horizons whose gain rows do not fit
+                                * in LDS: T > 74 at (8,2); needs `ws`) */
+  DMPC_LQR_PATH_CONTAINER = 7, /* lqr_kernel<..., PAD> of a larger shape, or lqr_wave_mfma_backward<..., PAD> + the
+                                * forward-only container kernel (needs `ws` unless the caller takes the gains) */
+  DMPC_LQR_PATH_TILED = 8,     /* lqr_tiled_kernel (any size: a workgroup per trajectory, matrices in `ws`) */
+  DMPC_LQR_PATH_WIDE = 9       /* lqr_wide_kernel (17 to 32 augmented columns, at most 16 states - (16,4), (16,8), (12,4),
+                                * (12,8), and padded inside them every shape with nx <= 16, nu <= 8, nx + nu >= 16 when
+                                * B % 4 == 0: four trajectories per wavefront, two registers per matrix row, outer products
+                                * on the matrix cores; plain and masked (LQR_active) solves alike; needs `ws` - without it,
+                                * with B < 4, T < 2 or B (nx+nu)^2 floats beyond 2^31 bytes the solve takes CONTAINER or
+                                * WAVE_MFMA) */
+};
 int dmpc_lqr_solve_path(int T, int B, int nx, int nu);
 
 /* ---- A. LqrRecursion (lqr/lqr_recursion.py:69-209) and LQR_active
@@ -100,7 +113,7 @@ int dmpc_lqr_solve(int T, int B, int nx, int nu, const float *C, const float *c,
  * forward solve, so it can reuse K_t, Quu_t, Qxu_t and only redo the affine terms (dmpc_lqr_saved_solve below), and
  * the co-states are the value function's gradients, lambda_t = V_t x_t + v_t (dmpc_lqr_kkt_grad_saved).
  * Served by the generated instruction stream that keeps F on chip only (dmpc_lqr_saving_available: dmpc_lqr_solve_path
- * == 4, B % 4 == 0, room in LDS for the staging area of the saved blocks; all pointers 16-byte aligned);
+ * == DMPC_LQR_PATH_ASM_STASH, B % 4 == 0, room in LDS for the staging area of the saved blocks; all pointers 16-byte aligned);
  * DMPC_E_UNSUPPORTED otherwise - the caller then uses dmpc_lqr_solve and the full second solve.
  * `info` [B], if given, is WRITTEN (0 = clean) rather than or-ed into: the caller need not clear it first. */
 int dmpc_lqr_saving_available(int T, int B, int nx, int nu);   /* 1: dmpc_lqr_solve_saving (and the saved-gains gradient) serves this size */
@@ -112,14 +125,14 @@ int dmpc_lqr_solve_saving(int T, int B, int nx, int nu, const float *C, const fl
 /* The re-solve: the LQR problem of an earlier dmpc_lqr_solve_saving (same C, F) with another affine cost term c
  * [T,B,ns], f = 0 and another x_init.  K_t does not depend on c; k_t = -Quu_t^-1 (c_u + F_u^T v_{t+1}),
  * v_t = q_x + Qxu_t k_t (lqr_recursion.py:92,119-120,152), then the rollout (:160-200).  C is not read.
- * DMPC_E_UNSUPPORTED unless dmpc_lqr_solve_path == 4 (generated stream, F kept on chip) and B % 4 == 0. */
+ * DMPC_E_UNSUPPORTED unless dmpc_lqr_solve_path == DMPC_LQR_PATH_ASM_STASH and B % 4 == 0. */
 int dmpc_lqr_saved_solve(int T, int B, int nx, int nu, const float *c, const float *F, const float *Ks,
                          const float *Quu, const float *Qxu, const float *x_init, float *x_out, float *u_out,
                          int32_t *info, dmpc_stream_t stream);
 
 /* backward(): gains only (lqr_recursion.py:69-158).  The `_ws` form takes the workspace of dmpc_lqr_workspace_bytes: the
- * shapes of kernel family 5 (nx + nu + 1 > 64: a workgroup per trajectory, matrices in the workspace) need it, every other
- * shape ignores it; the plain form is the `_ws` form with ws = NULL (DMPC_E_WORKSPACE for family 5). */
+ * shapes of DMPC_LQR_FAMILY_TILED need it, every other shape ignores it; the plain form is the `_ws` form with ws = NULL
+ * (DMPC_E_WORKSPACE for DMPC_LQR_FAMILY_TILED). */
 int dmpc_lqr_backward_sweep(int T, int B, int nx, int nu, const float *C, const float *c, const float *F,
                             const float *f, const uint8_t *u_zero_mask, float *Ks_out, float *ks_out,
                             int32_t *info, dmpc_stream_t stream);
@@ -163,9 +176,14 @@ int dmpc_lqr_kkt_grad_saved(int T, int B, int nx, int nu, const float *C, const 
  *      register-resident kernels in double for the shapes with an instantiation ((1,1) ... (12,3) at 16 lanes per trajectory,
  *      (16,4), (16,8), (32,8) at a wavefront per trajectory; plain and clamped) - the fast path - and, for every other shape
  *      (any size), one lane per trajectory with runtime dimensions and every matrix of a trajectory in `ws`
- *      (dmpc_lqr_f64_workspace_bytes, required in both cases).  dmpc_lqr_f64_path: 1 = 16-lane kernel, 2 = wavefront kernel,
- *      0 = one lane per trajectory.  Arrays are the float64 twins of dmpc_lqr_solve's / dmpc_lqr_kkt_grad's, same shapes;
- *      Ks_out / ks_out may be NULL (both). */
+ *      (dmpc_lqr_f64_workspace_bytes, required in both cases).  dmpc_lqr_f64_path says which (an int; <0 bad arguments).
+ *      Arrays are the float64 twins of dmpc_lqr_solve's / dmpc_lqr_kkt_grad's, same shapes; Ks_out / ks_out may be NULL
+ *      (both). */
+enum dmpc_lqr_f64_path_id {
+  DMPC_F64_PATH_LANE = 0,  /* one lane per trajectory, runtime dimensions */
+  DMPC_F64_PATH_ROW16 = 1, /* register-resident, 16 lanes per trajectory */
+  DMPC_F64_PATH_WAVE = 2   /* register-resident, a wavefront per trajectory */
+};
 int dmpc_lqr_f64_path(int nx, int nu);
 size_t dmpc_lqr_f64_workspace_bytes(int T, int B, int nx, int nu);
 int dmpc_lqr_solve_f64(int T, int B, int nx, int nu, const double *C, const double *c, const double *F, const double *f,
