@@ -14,22 +14,28 @@ weak and `value` = N*B*T*K / max-over-ranks time.  The timed region is ONE run o
 run-up and W warm-up steps; `ms_per_step` is its time over K.  Rank 0 prints ONE JSON line; with `--dump-outputs DIR` it
 also writes the (x*, u*) that the last timed step produced to DIR/x.npy and DIR/u.npy.
 
-Extra objects in that line:
-  roofline     dominant kernel vs the HBM roof: algorithmic bytes per launch (832 B per
+A plain run does only that: set up, run up, warm up, time the K steps, dump, print.  Everything else the benchmark
+measures or checks runs only with `--full` (the CPU legs before the GPU is touched, the rest after the timed region):
+
+  roofline     (always) dominant kernel vs the HBM roof: algorithmic bytes per launch (832 B per
                timestep-solve) / average launch duration measured with HIP events on
                the launch stream over the timed region; peak 8 TB/s (MI355X_MICROARCH.md).  The timed
                loop rotates over input sets (more than twice the 256 MiB Infinity Cache in total), so
-               every step streams its inputs from HBM; `frac_same_inputs` is the launch re-solving one set
-               (what rounds 1-2 reported), `box_copy_gbs` a plain copy on the same box, `kernel` the name
-               the library reports for the last launch (dmpc_last_kernel_name).
-  cpu_baseline the numpy float64 oracle (a port of the reference's algorithm; the reference's
+               every step streams its inputs from HBM; `kernel` is the name the library reports for the last
+               launch (dmpc_last_kernel_name).  With --full (N = 1) also `frac_same_inputs`, the launch
+               re-solving one set (what rounds 1-2 reported), and `box_copy_gbs`, a plain copy on the same box.
+  cpu_baseline (--full, N = 1) the numpy float64 oracle (a port of the reference's algorithm; the reference's
                Python cannot travel) timed on this host's cores on a bounded sample: one thread, and
-               (`cpu_baseline_mp`) the batch sharded over the host cores this process may use.
-  secondary    (N = 1, headline workload) the other numbers of SURVEY.md 8d, each timed with HIP events in this
-               run: DiffLqr forward + KKT backward at config 3, one shard of config 5 ((32,8), B=8192),
-               the MPC step at config 3, config 2's box-DDP solve, config 4's imitation step.
+               (`cpu_baseline_mp`) the batch sharded over the host cores this process may use; `parity`
+               compares the GPU solve of input set 0 with the oracle's (exit 3 beyond PARITY_TOL).
+  secondary    (--full, N = 1, headline workload) the other numbers of SURVEY.md 8d, each timed with HIP events in
+               this run: DiffLqr forward + KKT backward at config 3, one shard of config 5 ((32,8), B=8192),
+               the MPC step at config 3, config 2's box-DDP solve, config 4's imitation step, other shapes,
+               float64 (exit 4 when one of them failed, unless --allow-secondary-failure).
+  gather       (--full, --gather, N > 1) the solve / gather / serial times the overlapped figure is made of.
 
 Other invocations (the same JSON contract):
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full   # the headline line plus everything listed above
     python bench.py --workload cfg5-shard                    # one 8192-trajectory shard of config 5 on one GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus 8 --workload cfg5-shard --gather     # config 5 (65536 trajectories) + the all-gather of (x*, u*)
@@ -646,17 +652,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="headline", choices=sorted(WORKLOADS))
     ap.add_argument("--gather", action="store_true", help="all-gather (x*, u*) over RCCL inside the timed region, overlapped "
-                    "with the next solve (dist.GatherPipeline); the line then carries solve / gather / serial / overlapped times")
+                    "with the next solve (dist.GatherPipeline); with --full the line also carries solve / gather / serial / "
+                    "overlapped times")
     ap.add_argument("--gather-chunks", type=int, default=0, help="pieces per gathered tensor (0: by size, <= 64 MB each)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--cpu-procs", type=int, default=0, help="worker processes of the sharded CPU baseline "
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: "
+                    "CPU baselines and parity against the numpy oracle, the secondary workloads, shapes and float64, the "
+                    "same-inputs and plain-copy roofline context, the --gather split (without it: the headline line alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines, no parity check")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: time budget of the one-thread CPU baseline")
+    ap.add_argument("--cpu-procs", type=int, default=0, help="with --full: worker processes of the sharded CPU baseline "
                     "(default: the cores this process may use, at most 16 - a one-GPU box's CPU share)")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary measurements")
     ap.add_argument("--no-settle", action="store_true", help="time from a cold start: no run-up to the steady power state "
                     "before the warm-up steps (the first milliseconds of a job instead of its steady rate)")
     ap.add_argument("--allow-secondary-failure", action="store_true",
-                    help="exit 0 even when a secondary measurement raised (its error string is in the JSON line either way)")
+                    help="with --full: exit 0 even when a secondary measurement raised (its error string is in the JSON line "
+                    "either way)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (x*, u*: float32, time-major) as DIR/x.npy and DIR/u.npy; "
                     "a batch beyond %d MB is a fixed sample of trajectories (numpy seed 0), the same in every run" % (DUMP_BYTES // 10 ** 6))
@@ -677,9 +688,9 @@ def main():
         if strong_total % world:
             raise SystemExit("--workload %s splits %d trajectories over the ranks: --gpus %d does not divide it" % (args.workload, strong_total, world))
         B = strong_total // world
-    # the CPU legs run first, on rank 0 at N = 1 only: the worker pool is forked before this process touches the GPU
+    # the CPU legs (--full) run first, on rank 0 at N = 1 only: the worker pool is forked before this process touches the GPU
     cb = cb_mp = xr = ur = p_host = cb_sec = None
-    want_cpu = not args.no_cpu_baseline and world == 1 and B * T * (nx + nu) ** 2 <= 64 * 1024 * 1024
+    want_cpu = args.full and not args.no_cpu_baseline and world == 1 and B * T * (nx + nu) ** 2 <= 64 * 1024 * 1024
     if want_cpu:
         p_host = synthetic.make_lqr_problem(B, T, nx, nu, seed=rank)
         procs = args.cpu_procs or max(1, min(16, usable_cores()))
@@ -778,7 +789,7 @@ def main():
             dumped = dump_outputs(args.dump_outputs, {"x": GatherPipeline.as_time_major(gxs), "u": GatherPipeline.as_time_major(gus)})
     kern_name = kernel_name() if gx is None else None      # (with --gather the last launch is RCCL's, not ours)
     gather_info = None
-    if pipe is not None:
+    if pipe is not None and args.full:
         # the three times the overlapped figure is made of, every rank making the same number of calls (collectives inside):
         # the solve alone, the gather alone (side stream, waited for), and the two one after the other on one stream
         e0 = sets[0]
@@ -818,13 +829,15 @@ def main():
                        "what": "max over ranks; overlapped = the timed region of this line (solve k+1 on the launch stream "
                                "while the chunked all-gather of solve k's (x, u) runs on a side stream)"}
     # for the parity check: the solution of set 0, whatever set the last timed step solved
-    solve_device(d["C"], d["c"], d["F"], d["f"], d["x_init"], None, T, nx, nu, out=(x, u))
-    torch.cuda.synchronize()
-    x_host, u_host = x.cpu().numpy(), u.cpu().numpy()
-    # context for the number above (N = 1): the same launch re-solving ONE input set (what rounds 1-2 timed: a set that
-    # fits the Infinity Cache), and what this box's memory system sustains on a plain copy
+    x_host = u_host = None
+    if cb is not None:
+        solve_device(d["C"], d["c"], d["F"], d["f"], d["x_init"], None, T, nx, nu, out=(x, u))
+        torch.cuda.synchronize()
+        x_host, u_host = x.cpu().numpy(), u.cpu().numpy()
+    # context for the number above (--full, N = 1): the same launch re-solving ONE input set (what rounds 1-2 timed: a set
+    # that fits the Infinity Cache), and what this box's memory system sustains on a plain copy
     t_same = copy_gbs = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         del sets[1:]
         torch.cuda.empty_cache()
         if n_sets > 1:
@@ -857,7 +870,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak" if strong_total is None else "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": "%s: synthetic random LQR, B=%d per GPU%s, T=%d, n_x=%d, n_u=%d, fused "
                                    "solve_recursion (Riccati backward + rollout), inputs resident in HBM (streamed: "
                                    "input sets in rotation)"
@@ -924,7 +937,7 @@ def main():
             parity_ok = xe <= PARITY_TOL and ue <= PARITY_TOL
             out["parity"] = {"max_rel_err_x": xe, "max_rel_err_u": ue, "tolerance": PARITY_TOL, "ok": parity_ok,
                              "against": "oracle/lqr.py on identical inputs"}
-        if world == 1 and args.workload == "headline" and not args.no_secondary:
+        if args.full and world == 1 and args.workload == "headline" and not args.no_secondary:
             # the headline line must come out whatever happens to the secondary measurements
             sec = {}
             try:

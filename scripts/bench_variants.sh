@@ -3,7 +3,7 @@
 #   bash scripts/bench_variants.sh build_tmp/var/full_a.so build_tmp/var/full_b.so      [ROUNDS=2]
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in "$@"; do
-    DMPC_LIB=$(pwd)/$lib python bench.py --gpus 1 --steps 100 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "
+    DMPC_LIB=$(pwd)/$lib python bench.py --full --gpus 1 --steps 100 --warmup 20 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); s=d['secondary']
 g=lambda k,f: s.get(k,{}).get(f,float('nan'))

@@ -11,12 +11,12 @@ timeout 900 python -m pytest tests -m gpu -x -q 2>&1 | tail -25 | tee $OUT/pytes
 echo "== smoke"
 timeout 300 python __graft_entry__.py smoke 2>&1 | tail -5
 echo "== bench"
-timeout 600 python bench.py --steps 200 --warmup 20 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout 600 python bench.py --full --steps 200 --warmup 20 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 cat $OUT/bench_$TAG.json; tail -3 $OUT/bench_$TAG.err
 echo "== rocprofv3 kernel stats"
 REPO=$(pwd)
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o lqr -- python $REPO/bench.py --steps 100 --warmup 10 --no-cpu-baseline > $OUT/prof_$TAG.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o lqr -- python $REPO/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline > $OUT/prof_$TAG.log 2>&1
 cd $REPO
 find $OUT/prof_$TAG -name "*kernel_stats*" | head -3
 f=$(find $OUT/prof_$TAG -name "*kernel_stats.csv" | head -1)

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 cd /tmp
 pass() {
   name=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_${TAG}_$name -o p -- python $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/pmc_${TAG}_$name.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/pmc_${TAG}_$name -o p -- python $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/pmc_${TAG}_$name.log 2>&1
   f=$(find $OUT/pmc_${TAG}_$name -name "*counter_collection.csv" | head -1)
   echo "== $name: $f"
   [ -n "$f" ] && python3 - "$f" <<'PY'

@@ -3,7 +3,7 @@
 REPO=$(pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
 rm -f $OUT/r02_pmc_headline.txt
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  timeout 600 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $OUT/pmc_r02h_$ctr -o p -- python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $OUT/pmc_r02h_$ctr.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $OUT/pmc_r02h_$ctr -o p -- python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $OUT/pmc_r02h_$ctr.log 2>&1
   f=$(find $OUT/pmc_r02h_$ctr -name "*counter_collection.csv" | head -1)
   python3 - "$f" $ctr <<'PY' | tee -a $OUT/r02_pmc_headline.txt
 import csv, sys

@@ -23,15 +23,15 @@ for k, v in sorted(agg.items()):
 PY
 }
 rm -f $OUT/r02_pmc_summary.txt
-stats bench python3 $REPO/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-secondary
+stats bench python3 $REPO/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-secondary
 stats rows python3 $REPO/scripts/rows_workload.py
-stats secondary python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline
-pmc fetch lqr_asm "FETCH_SIZE" python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary
-pmc write lqr_asm "WRITE_SIZE" python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary
-pmc w328_mix wave_mfma "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY" python3 $REPO/bench.py --workload cfg5-shard --steps 3 --warmup 1 --no-cpu-baseline
-pmc w328_mem wave_mfma "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY" python3 $REPO/bench.py --workload cfg5-shard --steps 3 --warmup 1 --no-cpu-baseline
-pmc w328_fetch wave_mfma "FETCH_SIZE" python3 $REPO/bench.py --workload cfg5-shard --steps 3 --warmup 1 --no-cpu-baseline
-pmc w328_write wave_mfma "WRITE_SIZE" python3 $REPO/bench.py --workload cfg5-shard --steps 3 --warmup 1 --no-cpu-baseline
+stats secondary python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
+pmc fetch lqr_asm "FETCH_SIZE" python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary
+pmc write lqr_asm "WRITE_SIZE" python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary
+pmc w328_mix wave_mfma "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY" python3 $REPO/bench.py --full --workload cfg5-shard --steps 3 --warmup 1 --no-cpu-baseline
+pmc w328_mem wave_mfma "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_ANY" python3 $REPO/bench.py --full --workload cfg5-shard --steps 3 --warmup 1 --no-cpu-baseline
+pmc w328_fetch wave_mfma "FETCH_SIZE" python3 $REPO/bench.py --full --workload cfg5-shard --steps 3 --warmup 1 --no-cpu-baseline
+pmc w328_write wave_mfma "WRITE_SIZE" python3 $REPO/bench.py --full --workload cfg5-shard --steps 3 --warmup 1 --no-cpu-baseline
 cd $REPO
 # DiffLqr forward + backward loop, with saved gains and with the full second solve
 cd /tmp

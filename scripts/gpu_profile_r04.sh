@@ -35,9 +35,9 @@ if [ "$PART" = "A" ]; then
   DMPC_PARITY_LOG=$OUT/parity_log.txt timeout -k 10 900 python3 -m pytest tests -m gpu -q > $OUT/gpu_tests.log 2>&1; tail -2 $OUT/gpu_tests.log
   { python3 scripts/parity_margins.py --condense $OUT/parity_log.txt; echo; timeout -k 10 600 python3 scripts/parity_margins.py --out $OUT/parity_margins_big.txt > /dev/null 2>&1; cat $OUT/parity_margins_big.txt; } > $OUT/parity_margins.txt
   rm -f $OUT/parity_log.txt $OUT/parity_margins_big.txt
-  timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err; tail -c 400 $OUT/bench_line.json
-  stats bench_headline python3 $REPO/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-secondary
-  stats bench_secondary python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline
+  timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err; tail -c 400 $OUT/bench_line.json
+  stats bench_headline python3 $REPO/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-secondary
+  stats bench_secondary python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
   stats rows python3 $REPO/scripts/rows_workload.py
   { timeout -k 10 300 python3 scripts/size_sweep.py; SHAPES="4x2,3x1,6x2,4x4,8x4,12x3,6x3,13x2,9x4,11x4,5x5,12x4,12x8,16x4,16x8,13x3,10x6,15x7,20x6,17x4,24x8,24x4,32x4" timeout -k 10 300 python3 scripts/size_sweep.py; } > $OUT/size_sweep_steady.txt 2>&1
   timeout -k 10 300 python3 scripts/f64_timing.py > $OUT/f64_timing.txt 2>&1
@@ -47,12 +47,12 @@ if [ "$PART" = "A" ]; then
   ls -la $OUT
 else
   rm -f $OUT/pmc_summary.txt
-  B="python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
+  B="python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
   pmc headline_fetch lqr_asm "FETCH_SIZE" $B
   pmc headline_write lqr_asm "WRITE_SIZE" $B
   pmc f64_fetch lqr_f64_row "FETCH_SIZE" python3 $REPO/scripts/f64_timing.py headline
   pmc f64_write lqr_f64_row "WRITE_SIZE" python3 $REPO/scripts/f64_timing.py headline
-  W="python3 $REPO/bench.py --workload cfg5-shard --steps 3 --warmup 1 --no-cpu-baseline"
+  W="python3 $REPO/bench.py --full --workload cfg5-shard --steps 3 --warmup 1 --no-cpu-baseline"
   pmc w328_fetch wave_mfma "FETCH_SIZE" $W
   pmc w328_write wave_mfma "WRITE_SIZE" $W
   pmc w328_mix wave_mfma "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY" $W

@@ -35,9 +35,9 @@ if [ "$PART" = "A" ]; then
   DMPC_PARITY_LOG=$OUT/parity_log.txt timeout -k 10 900 python3 -m pytest tests -m gpu -q > $OUT/gpu_tests.log 2>&1; tail -2 $OUT/gpu_tests.log
   { python3 scripts/parity_margins.py --condense $OUT/parity_log.txt; echo; timeout -k 10 600 python3 scripts/parity_margins.py --out $OUT/parity_margins_big.txt > /dev/null 2>&1; cat $OUT/parity_margins_big.txt; } > $OUT/parity_margins.txt
   rm -f $OUT/parity_log.txt $OUT/parity_margins_big.txt
-  timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err; tail -c 400 $OUT/bench_line.json
-  stats bench_headline python3 $REPO/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-secondary
-  stats bench_secondary python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline
+  timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_line.json 2> $OUT/bench_line.err; tail -c 400 $OUT/bench_line.json
+  stats bench_headline python3 $REPO/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-secondary
+  stats bench_secondary python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline
   stats rows python3 $REPO/scripts/rows_workload.py
   { timeout -k 10 300 python3 scripts/size_sweep.py; SHAPES="4x2,3x1,6x2,4x4,8x4,12x3,6x3,13x2,9x4,11x4,5x5,12x4,12x8,16x4,16x8,13x3,10x6,15x7,20x6,17x4,24x8,24x4,32x4" timeout -k 10 300 python3 scripts/size_sweep.py; } > $OUT/size_sweep_steady.txt 2>&1
   timeout -k 10 300 python3 scripts/f64_timing.py > $OUT/f64_timing.txt 2>&1
@@ -50,7 +50,7 @@ if [ "$PART" = "A" ]; then
   ls -la $OUT
 else
   rm -f $OUT/pmc_summary.txt
-  B="python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
+  B="python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
   pmc headline_fetch lqr_asm "FETCH_SIZE" $B
   pmc headline_write lqr_asm "WRITE_SIZE" $B
   pmc f64_fetch lqr_f64_row "FETCH_SIZE" python3 $REPO/scripts/f64_timing.py headline
@@ -67,7 +67,7 @@ else
   pmc s84_mix "lqr_kernel<8, 4, 16" "SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" $S
   pmc s44_mix "lqr_asm_kernel<4, 4" "SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" $S
   unset SHAPES
-  B="python3 $REPO/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
+  B="python3 $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary"
   pmc s82_mix "lqr_asm_kernel<8, 2" "SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" $B
   python3 $REPO/scripts/shape_floor.py $OUT/pmc_summary.txt > $OUT/shape_floor.txt
   pmc difflqr_fetch dmpc "FETCH_SIZE" python3 $REPO/scripts/difflqr_loop.py

@@ -53,8 +53,32 @@ def test_every_name_is_defined(script):
 def test_bench_command_line_is_the_drivers():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
-    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--gather", "--allow-secondary-failure"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--gather", "--allow-secondary-failure", "--full",
+                 "--dump-outputs"):
         assert flag in r.stdout
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_cpu_legs_run_with_full_only(monkeypatch, full):
+    """a plain run goes straight to the GPU (here: to the message that it needs one) without touching the CPU baselines;
+    `--full` runs all three of them first, before the GPU is touched"""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    called = []
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    monkeypatch.setattr(bench.synthetic, "make_lqr_problem", lambda *a, **k: called.append("problem") or {})
+    monkeypatch.setattr(bench, "cpu_baseline_multiprocess", lambda *a, **k: called.append("mp") or {})
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: called.append("one") or ({}, None, None))
+    monkeypatch.setattr(bench, "secondary_cpu_baselines", lambda *a, **k: called.append("secondary") or {})
+    for var in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--cpu-procs", "2"]
+                        + (["--full"] if full else []))
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert "needs an MI355X" in str(e.value)
+    assert called == (["problem", "mp", "one", "secondary"] if full else [])
 
 
 def test_the_rccl_argument_path_up_to_init_process_group(monkeypatch):

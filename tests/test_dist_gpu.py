@@ -113,10 +113,10 @@ def test_two_ranks_over_rccl_on_two_devices(tmp_path):
 
 
 def test_bench_py_runs_with_two_ranks_and_the_overlapped_gather(tmp_path):
-    """`bench.py --gpus 2 --gather` executed for real (everything beyond init_process_group was unexecuted code):
-    two ranks on this box's one GPU through the rehearsal knobs (gloo, both ranks on device 0) - init, sharded inputs, the
-    GatherPipeline in the timed region, barrier + max-over-ranks timing, rank 0's ONE JSON line with the solve / gather /
-    serial / overlapped split.  The numbers are not scaling numbers (one device, host-staged collectives); the path is."""
+    """`bench.py --gpus 2 --gather --full` executed for real (everything beyond init_process_group was unexecuted
+    code): two ranks on this box's one GPU through the rehearsal knobs (gloo, both ranks on device 0) - init, sharded inputs,
+    the GatherPipeline in the timed region, barrier + max-over-ranks timing, rank 0's ONE JSON line with the solve / gather /
+    serial / overlapped split (--full).  The numbers are not scaling numbers (one device, host-staged collectives); the path is."""
     import json
     port = free_port()
     procs = []
@@ -124,7 +124,7 @@ def test_bench_py_runs_with_two_ranks_and_the_overlapped_gather(tmp_path):
         env = dict(os.environ, RANK=str(rank), WORLD_SIZE="2", LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
                    MASTER_PORT=str(port), DMPC_BENCH_BACKEND="gloo", DMPC_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup",
-                                       "1", "--workload", "pendulum", "--gather", "--gather-chunks", "2"], env=env,
+                                       "1", "--workload", "pendulum", "--gather", "--gather-chunks", "2", "--full"], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = []
     for p in procs:
