@@ -70,6 +70,10 @@ SIGNATURES = {
     "dmpc_box_ddp": (_c_i, [_c_i] * 4 + [_c_f] * 5 + [_c_i, _c_f] + [_c_f] * 3 +
                      [ctypes.c_float, _c_i, ctypes.c_float, _c_i, ctypes.c_float, _c_i, _c_i, _c_i, _c_i] +
                      [_c_f] * 7 + [_c_sz, _c_f, _c_f]),
+    "dmpc_il_n_params": (_c_i, [_c_i, _c_i]),
+    "dmpc_il_batch_begin": (_c_i, [_c_i] * 6 + [_c_f] * 11 + [_c_f]),
+    "dmpc_il_loss": (_c_i, [_c_i] * 4 + [_c_f] * 6 + [_c_f]),
+    "dmpc_il_param_step": (_c_i, [_c_i, _c_i] + [_c_f] * 5 + [_c_i, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_f]),
 }
 
 _lib = None

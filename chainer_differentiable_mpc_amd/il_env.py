@@ -126,12 +126,18 @@ class IL_Env:
 
 class Pendulum_Net_cost_logit(torch.nn.Module):
     """learnable pendulum cost: q = sigmoid(learn_q_logit), p = sqrt(q) * learn_p  (pendulum_net.py:12-39)"""
+    kind = 0        # the parameterisation's code in the C-ABI's dmpc_il_* entry points
 
     def __init__(self, n_sc, device="cuda", dtype=torch.float32):
         super().__init__()
         self.n_sc = n_sc
         self.learn_q_logit = torch.nn.Parameter(torch.zeros(n_sc, device=device, dtype=dtype))
         self.learn_p = torch.nn.Parameter(torch.zeros(n_sc, device=device, dtype=dtype))
+
+    def cost_map(self):
+        """(Q [n_sc, n_sc], p [n_sc]) = (diag(q), sqrt(q) * learn_p), what `forward` hands to the solver"""
+        q = torch.sigmoid(self.learn_q_logit)
+        return torch.diag(q), torch.sqrt(q) * self.learn_p
 
     def forward(self, xinit, env, train_warm_start_idxs=None):
         q = torch.sigmoid(self.learn_q_logit)

@@ -177,6 +177,15 @@ class _MPCstepTiledFn(torch.autograd.Function):
                 dp.to(device=qdev, dtype=qd), None, None, None, None)
 
 
+def tiled_gradient_inputs(out):
+    """read-only: (spec, retained) that `BoxDDP` handed to the `_MPCstepTiledFn` node of the solve whose output is `out`
+    (x or u), for a caller that forms the gradient itself with `tiled_cost_gradient`; None if `out` has no such node"""
+    node = getattr(out, "grad_fn", None)
+    if node is None or not hasattr(node, "retained") or not hasattr(node, "spec"):
+        return None
+    return node.spec, node.retained
+
+
 class MPCstep:
     """MPC forward backward calculation (mpc/mpc_step.py:33)."""
 

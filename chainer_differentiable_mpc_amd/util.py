@@ -30,6 +30,14 @@ class TiledQuadCost(QuadCost):
         self.Q, self.p = Q, p
         return self
 
+    @classmethod
+    def from_tiles(cls, C, c, Q, p):
+        """around tiles the caller already holds (C [T,B,ns,ns], c [T,B,ns] equal to Q, p repeated): no copy, so a solver
+        called again sees the same buffers (the imitation driver's device update writes them in place)"""
+        self = super().__new__(cls, C, c)
+        self.Q, self.p = Q, p
+        return self
+
 
 def bmv(a, x):
     assert a.shape[0] == x.shape[0], "batch mismatch"

@@ -351,6 +351,29 @@ int dmpc_mpc_step_backward(int T, int B, int nx, int nu, const float *C_hat, con
                            const float *detach_norm, const int32_t *detach_flag, float detach_eps, void *ws,
                            size_t ws_bytes, int32_t *info, dmpc_stream_t stream);
 
+/* Imitation-learning update (env_dx/il_exp.py:191-316; il_exp.py drives it).  A cost net `kind` (0 logit, 1 lower
+ * triangle, 2 logit + observation matrix, 3 lower triangle + observation matrix: env_dx/pendulum_net.py; n_sc <= 8, kinds 2-3
+ * need n_sc = 4) has the parameter vector [learn_q_logit (n_sc), learn_p (n_sc), lower_without_diag (n_sc(n_sc-1)/2, kinds
+ * 1 and 3 only)].  A split of the data set stays on the device: tau [N,T,ns], its warm-start controls warm [N,T,nu], a batch
+ * is idx int32 [B] (an index outside [0, N) reads zeros and writes nothing).
+ * dmpc_il_n_params: the length of the parameter vector, or DMPC_E_UNSUPPORTED.
+ * dmpc_il_batch_begin: x_init [B,nx] = tau[idx, 0, :nx], us [T,B,nu] = tau[idx, :, nx:] time-major, u_init [T,B,nu] (or
+ *   NULL) = warm[idx] time-major (zeros if warm is NULL); (Q [ns,ns], p [ns]) = the cost map at `params`, tiled to
+ *   C [T,B,ns,ns], c [T,B,ns].  One launch.
+ * dmpc_il_loss: *loss = mean((u - us)^2) over T*B*nu (one workgroup, fixed summation order); grad_u (or NULL) =
+ *   2 (u - us) / (T*B*nu); warm (or NULL): warm[idx[b], t, :] = u[t, b, :].  One launch.
+ * dmpc_il_param_step: grad = d loss / d params from dQ [ns,ns], dp [ns] through the cost map; then RMSprop on the groups
+ *   set in enable_mask (1 learn_q_logit, 2 learn_p, 4 lower_without_diag): ms = alpha ms + (1 - alpha) grad^2,
+ *   params -= lr grad / (sqrt(ms) + eps); a disabled group's params and ms are left untouched.  One workgroup. */
+int dmpc_il_n_params(int kind, int n_sc);
+int dmpc_il_batch_begin(int kind, int N, int T, int B, int nx, int nu, const float *tau, const float *warm,
+                        const int32_t *idx, const float *params, float *x_init, float *us, float *u_init, float *Q,
+                        float *p, float *C, float *c, dmpc_stream_t stream);
+int dmpc_il_loss(int N, int T, int B, int nu, const float *u, const float *us, const int32_t *idx, float *loss,
+                 float *grad_u, float *warm, dmpc_stream_t stream);
+int dmpc_il_param_step(int kind, int n_sc, const float *dQ, const float *dp, float *params, float *ms, float *grad,
+                       int enable_mask, float lr, float alpha, float eps, dmpc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
