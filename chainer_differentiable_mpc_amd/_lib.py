@@ -74,6 +74,12 @@ SIGNATURES = {
     "dmpc_il_batch_begin": (_c_i, [_c_i] * 6 + [_c_f] * 11 + [_c_f]),
     "dmpc_il_loss": (_c_i, [_c_i] * 4 + [_c_f] * 6 + [_c_f]),
     "dmpc_il_param_step": (_c_i, [_c_i, _c_i] + [_c_f] * 5 + [_c_i, ctypes.c_float, ctypes.c_float, ctypes.c_float, _c_f]),
+    "dmpc_lqr_shared_workspace_bytes": (_c_sz, [_c_i] * 4),
+    "dmpc_lqr_shared_saved_bytes": (_c_sz, [_c_i] * 3),
+    "dmpc_lqr_shared_grad_workspace_bytes": (_c_sz, [_c_i] * 4),
+    "dmpc_lqr_shared_solve": (_c_i, [_c_i] * 4 + [ctypes.c_uint32] + [_c_f] * 8 + [_c_sz, _c_f, _c_f]),
+    "dmpc_lqr_shared_kkt_grad": (_c_i, [_c_i] * 4 + [ctypes.c_uint32] + [_c_f] * 8 + [_c_i] + [_c_f] * 6
+                                 + [_c_sz, _c_f, _c_f]),
 }
 
 _lib = None

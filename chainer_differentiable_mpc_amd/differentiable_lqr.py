@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, lqr_shared
 from .lqr_recursion import (_as_tensor, _device_of, _workspace, saving_solve_available, solve_device, solve_device_f64,
                             solve_saving_device)
 from .util import expand_time_batch
@@ -148,6 +148,8 @@ class DiffLqr:
     # -- computation on the device -------------------------------------------------------------
     def _forward_impl(self, x_init, C, c, F, f):
         x_init, C, c, F, f = (_as_tensor(t) for t in (x_init, C, c, F, f))
+        if not lqr_shared.is_full(C, c, F, f):
+            return self._forward_reduced(x_init, C, c, F, f)
         T, B, nx, nu, ns = self.T, self.n_batch, self.n_state, self.n_ctrl, self.n_sc
         assert list(x_init.shape) == [B, nx]
         assert list(C.shape) == [T, B, ns, ns], "C dim mismatch"
@@ -186,6 +188,29 @@ class DiffLqr:
                               out_device=C.device, versions=tuple(t._version for t in d[:4]))
         return x.to(device=C.device, dtype=C.dtype), u.to(device=C.device, dtype=C.dtype)
 
+    def _forward_reduced(self, x_init, C, c, F, f):
+        """inputs without a batch axis (lqr_shared.py): one shared Riccati sweep where C and F have none, else expanded and
+        materialised into today's dense path"""
+        T, B, nx, nu = self.T, self.n_batch, self.n_state, self.n_ctrl
+        assert list(x_init.shape) == [B, nx]
+        lqr_shared.check_shapes(T, B, nx, nu, C, c, F, f)
+        originals = (x_init, C, c, F)
+        if lqr_shared.classify(T, nx, nu, C, c, F, f, self.precision) == "expand":
+            x, u = self._forward_impl(x_init, *lqr_shared.expand_full(T, B, C, c, F, f))
+            # the materialised copies are what the dense path retained: the caller's tensors are checked in backward too
+            self._retained["reduce"] = (tuple(C.shape), tuple(c.shape), tuple(F.shape), None if f is None else tuple(f.shape))
+            self._retained["originals"] = (originals, tuple(t._version for t in originals))
+            return x, u
+        dev = _device_of(C, c, F, x_init)
+        d = [_lib.f32c(t.detach() if t is not None else None, dev) for t in (x_init, C, c, F, f)]
+        layout = lqr_shared.layout_of(C, c, F, f)
+        self.info = torch.zeros(B, dtype=torch.int32, device=dev)
+        x, u, ws = lqr_shared.solve_device(d[1], d[2], d[3], d[4], d[0], layout, T, nx, nu, info=self.info)
+        self._retained = dict(x_init=d[0], C=d[1], c=d[2], F=d[3], x=x, u=u, saved=None,
+                              shared=(layout, ws, None if f is None else tuple(f.shape)), out_dtype=C.dtype,
+                              out_device=C.device, versions=tuple(t._version for t in d[:4]))
+        return x.to(device=C.device, dtype=C.dtype), u.to(device=C.device, dtype=C.dtype)
+
     # -- reference API ---------------------------------------------------------------------------
     def forward(self, inputs):
         """inputs = (x_init, C, c, F, f) -> (x, u); retains inputs 0-3 and both outputs (:65-76)"""
@@ -201,13 +226,40 @@ class DiffLqr:
     __call__ = apply
 
     def backward(self, target_input_indexes, grad_outputs, retained=None):
-        """-> (d_x_init, dC, dc, dF, df) for upstream (grad_x, grad_u)  (differentiable_lqr.py:78-142)"""
+        """-> (d_x_init, dC, dc, dF, df) for upstream (grad_x, grad_u)  (differentiable_lqr.py:78-142).  Each gradient has
+        its input's shape: reduced inputs (lqr_shared.py) get gradients summed over the axes they lack, on the device."""
         r = self._retained if retained is None else retained
         assert r is not None, "backward() before forward()"
         now = tuple(r[k]._version for k in ("x_init", "C", "c", "F"))
         if now != r.get("versions", now):
             raise RuntimeError("DiffLqr.backward: x_init, C, c or F was modified in place after forward() (tensor versions "
                                "%r -> %r); the retained solution and gains belong to the old values" % (r["versions"], now))
+        if "originals" in r:
+            ts, was = r["originals"]
+            now = tuple(t._version for t in ts)
+            if now != was:
+                raise RuntimeError("DiffLqr.backward: x_init, C, c or F was modified in place after forward() (tensor "
+                                   "versions %r -> %r); the retained solution and gains belong to the old values" % (was, now))
+        if r.get("shared") is not None:
+            return self._backward_shared(r, grad_outputs)
+        out = self._backward_dense(r, grad_outputs)
+        if r.get("reduce") is not None:
+            out = (out[0],) + tuple(lqr_shared.reduce_to(g, s) for g, s in zip(out[1:], r["reduce"]))
+        return out
+
+    def _backward_shared(self, r, grad_outputs):
+        T, B, nx, nu = self.T, self.n_batch, self.n_state, self.n_ctrl
+        grad_x, grad_u = grad_outputs
+        dev = r["C"].device
+        gx = _lib.f32c(_as_tensor(grad_x), dev) if grad_x is not None else torch.zeros((T, B, nx), device=dev)
+        gu = _lib.f32c(_as_tensor(grad_u), dev) if grad_u is not None else torch.zeros((T, B, nu), device=dev)
+        assert list(gx.shape) == [T, B, nx] and list(gu.shape) == [T, B, nu]
+        layout, ws, f_shape = r["shared"]
+        out = lqr_shared.kkt_grad_device(r["C"], r["c"], r["F"], f_shape, r["x"], r["u"], ws, gx, gu, layout, T, nx, nu,
+                                         strict_math=self.strict_math, workspace=_workspace)
+        return tuple(None if g is None else g.to(device=r["out_device"], dtype=r["out_dtype"]) for g in out)
+
+    def _backward_dense(self, r, grad_outputs):
         T, B, nx, nu = self.T, self.n_batch, self.n_state, self.n_ctrl
         grad_x, grad_u = grad_outputs
         dev = r["C"].device
@@ -226,11 +278,15 @@ class DiffLqr:
 
 
 class LqrNet(torch.nn.Module):
-    """LQR layer whose dynamics [A|B] are learnable (differentiable_lqr.py:145-198)."""
+    """LQR layer whose dynamics [A|B] are learnable (differentiable_lqr.py:145-198).
+    shared=True (not in the reference's signature): [A|B] goes to the layer as one [nx,ns] matrix instead of being expanded
+    over time and batch; with a C that has no batch axis either, the solve is one Riccati sweep for the whole batch and the
+    gradient of [A|B] is reduced on the device (lqr_shared.py)."""
 
-    def __init__(self, T, n_batch, n_state, n_ctrl, seed, dtype=torch.float64):
+    def __init__(self, T, n_batch, n_state, n_ctrl, seed, dtype=torch.float64, shared=False):
         super().__init__()
         self.T, self.n_batch, self.n_state, self.n_ctrl = T, n_batch, n_state, n_ctrl
+        self.shared = bool(shared)
         self.n_sc = n_ctrl + n_state
         np.random.seed(seed)                      # same draws as the reference (:167-172)
         alpha = 0.2
@@ -243,17 +299,22 @@ class LqrNet(torch.nn.Module):
     def forward(self, inputs):
         x_init, C, c, f = inputs
         ab_cat = torch.cat((self.A, self.B), dim=1)
+        if self.shared:
+            return self.lqr_layer.apply((x_init, C, c, ab_cat, f))
         large_f_learner = expand_time_batch(ab_cat, self.T - 1, self.n_batch)
         assert list(large_f_learner.shape) == [self.T - 1, self.n_batch, self.n_state, self.n_sc]
         return self.lqr_layer.apply((x_init, C, c, large_f_learner, f))
 
 
 class LqrNet_cost_dx(torch.nn.Module):
-    """LQR layer with learnable cost (C, c) and dynamics (differentiable_lqr.py:201-248)."""
+    """LQR layer with learnable cost (C, c) and dynamics (differentiable_lqr.py:201-248).
+    shared=True (not in the reference's signature): C [ns,ns], c [ns] and [A|B] go to the layer without being expanded over
+    time and batch - one Riccati sweep for the whole batch, parameter-shaped gradients (lqr_shared.py)."""
 
-    def __init__(self, T, n_batch, n_state, n_ctrl, seed, dtype=torch.float64):
+    def __init__(self, T, n_batch, n_state, n_ctrl, seed, dtype=torch.float64, shared=False):
         super().__init__()
         self.T, self.n_batch, self.n_state, self.n_ctrl = T, n_batch, n_state, n_ctrl
+        self.shared = bool(shared)
         self.n_sc = n_ctrl + n_state
         np.random.seed(seed)                      # (:222-231)
         alpha = 0.2
@@ -270,6 +331,8 @@ class LqrNet_cost_dx(torch.nn.Module):
     def forward(self, inputs):
         x_init, f = inputs
         ab_cat = torch.cat((self.A, self.B), dim=1)
+        if self.shared:
+            return self.lqr_layer.apply((x_init, self.C, self.c, ab_cat, f))
         large_f_learner = expand_time_batch(ab_cat, self.T - 1, self.n_batch)
         C = expand_time_batch(self.C, self.T, self.n_batch)
         c = expand_time_batch(self.c, self.T, self.n_batch)

@@ -53,11 +53,15 @@ def shard_batch(t, rank, world, batch_dim=1):
 
 
 def shard_problem(x_init, C, c, F, f, rank=None, world=None):
-    """(x_init [B,nx], C [T,B,..], c, F, f|None) -> this rank's shard"""
+    """(x_init [B,nx], C [T,B,..], c, F, f|None) -> this rank's shard.  An input without a batch axis (C [ns,ns] / [T,ns,ns],
+    c [ns] / [T,ns], F [nx,ns] / [T-1,nx,ns], f [nx] / [T-1,nx]: lqr_shared.py) is the same on every rank and passes
+    through unsharded; its gradient is then parameter-shaped already, ready for `all_reduce_param_grad`."""
     rank = dist.get_rank() if rank is None else rank
     world = dist.get_world_size() if world is None else world
-    return (shard_batch(x_init, rank, world, 0), shard_batch(C, rank, world), shard_batch(c, rank, world),
-            shard_batch(F, rank, world), shard_batch(f, rank, world))
+
+    def part(t, batch_dims):
+        return shard_batch(t, rank, world) if t is not None and t.dim() == batch_dims else t
+    return (shard_batch(x_init, rank, world, 0), part(C, 4), part(c, 3), part(F, 4), part(f, 3))
 
 
 def all_gather_batch(local, n_batch_total=None, batch_dim=1, group=None):

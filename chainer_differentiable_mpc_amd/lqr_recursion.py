@@ -9,7 +9,7 @@ import collections
 
 import torch
 
-from . import _lib
+from . import _lib, lqr_shared
 
 
 def _as_tensor(v):
@@ -52,6 +52,21 @@ class LqrRecursion:
         self.F = _as_tensor(large_f)
         self.f = _as_tensor(f)
         self.T = int(T)
+        # inputs without a batch axis (lqr_shared.py): C [ns,ns] / [T,ns,ns], c [ns] / [T,ns], F [nx,ns] / [T-1,nx,ns],
+        # f [nx] / [T-1,nx] - solve_recursion() runs one shared Riccati sweep where neither C nor F has one, everything
+        # else (backward(), forward(Ks, ks), float64, larger sizes, u_zero_Index) expands them into today's dense path
+        self._reduced = not (len(self.C.shape) == 4 and len(self.c.shape) == 3 and
+                             (self.F is None or len(self.F.shape) == 4) and (self.f is None or len(self.f.shape) == 3))
+        if self._reduced:
+            self.n_batch = self.x_init.shape[0]
+            self.n_state = int(n_state)
+            self.n_ctrl = int(n_ctrl)
+            self.n_sc = self.n_state + self.n_ctrl
+            self.u_zero_Index = _as_tensor(u_zero_Index)
+            assert list(self.x_init.shape) == [self.n_batch, self.n_state]
+            lqr_shared.check_shapes(self.T, self.n_batch, self.n_state, self.n_ctrl, self.C, self.c, self.F, self.f)
+            self._init_tail()
+            return
         self.n_batch = self.C.shape[1]
         self.n_state = int(n_state)
         self.n_ctrl = int(n_ctrl)
@@ -68,6 +83,9 @@ class LqrRecursion:
                 list(self.F.shape[1:]) == [self.n_batch, self.n_state, self.n_sc], "F dim mismatch"
         if self.f is not None:
             assert list(self.f.shape) == [self.T - 1, self.n_batch, self.n_state], " f dim mismatch"
+        self._init_tail()
+
+    def _init_tail(self):
         if self.u_zero_Index is not None:
             assert list(self.u_zero_Index.shape) == [self.T, self.n_batch, self.n_ctrl]
         self._out_dtype = self.C.dtype if self.C.dtype.is_floating_point else torch.float32
@@ -76,12 +94,19 @@ class LqrRecursion:
         self.info = None
 
     # -- marshalling -------------------------------------------------------------------------
+    def _full_inputs(self):
+        """(C, c, F, f) of today's full shapes: reduced inputs as expand views (materialised by the callers)"""
+        if not self._reduced:
+            return self.C, self.c, self.F, self.f
+        return lqr_shared.expand_full(self.T, self.n_batch, self.C, self.c, self.F, self.f)
+
     def _dev_inputs(self):
         d = self._dev
         mask = None
         if self.u_zero_Index is not None:
             mask = self.u_zero_Index.to(device=d).to(torch.uint8).contiguous()
-        return (_lib.f32c(self.C, d), _lib.f32c(self.c, d), _lib.f32c(self.F, d), _lib.f32c(self.f, d),
+        C, c, F, f = self._full_inputs()
+        return (_lib.f32c(C, d), _lib.f32c(c, d), _lib.f32c(F, d), _lib.f32c(f, d),
                 _lib.f32c(self.x_init, d), mask)
 
     def _out(self, t):
@@ -94,7 +119,8 @@ class LqrRecursion:
     # -- reference API -----------------------------------------------------------------------
     def backward(self):
         """Riccati backward recursion -> (Ks, ks): lists of T per-step gains [B,nu,nx], [B,nu]
-        in forward time order (lqr_recursion.py:69-158)."""
+        in forward time order (lqr_recursion.py:69-158).  Inputs without a batch axis are expanded and materialised
+        into the dense sweep."""
         lib = _lib.load()
         _lib.require_gpu()
         C, c, F, f, _, mask = self._dev_inputs()
@@ -115,7 +141,8 @@ class LqrRecursion:
         return [Ks[t] for t in range(T)], [ks[t] for t in range(T)]
 
     def forward(self, Ks, ks):
-        """closed-loop rollout with the given gains -> (x [T,B,nx], u [T,B,nu]) (lqr_recursion.py:160-200)"""
+        """closed-loop rollout with the given gains -> (x [T,B,nx], u [T,B,nu]) (lqr_recursion.py:160-200).  Inputs without
+        a batch axis are expanded and materialised into the dense rollout."""
         assert len(Ks) == self.T, "Ks length error"
         lib = _lib.load()
         _lib.require_gpu()
@@ -136,12 +163,22 @@ class LqrRecursion:
         return self._out(x), self._out(u)
 
     def solve_recursion(self):
-        """backward + forward in ONE fused launch -> (x, u) (lqr_recursion.py:202-209)"""
+        """backward + forward in ONE fused launch -> (x, u) (lqr_recursion.py:202-209).  C and F without a batch axis (float32,
+        nx <= 32, nu <= 8, no u_zero_Index): one shared Riccati sweep for the whole batch, then the per-trajectory affine
+        sweep and rollout (dmpc_lqr_shared_solve)."""
+        if self._reduced and self.u_zero_Index is None and lqr_shared.classify(
+                self.T, self.n_state, self.n_ctrl, self.C, self.c, self.F, self.f, self.precision) == "shared":
+            d = self._dev
+            C, c, F, f, x0 = (_lib.f32c(t, d) for t in (self.C, self.c, self.F, self.f, self.x_init))
+            x, u, _ = lqr_shared.solve_device(C, c, F, f, x0, lqr_shared.layout_of(self.C, self.c, self.F, self.f), self.T,
+                                              self.n_state, self.n_ctrl, info=self._new_info())
+            return self._out(x), self._out(u)
         if self.precision == "float64":
             d = self._dev
             f64 = lambda t: None if t is None else t.to(device=d, dtype=torch.float64).contiguous()
             mask = None if self.u_zero_Index is None else self.u_zero_Index.to(device=d).to(torch.uint8).contiguous()
-            x, u, _, _ = solve_device_f64(f64(self.C), f64(self.c), f64(self.F), f64(self.f), f64(self.x_init), mask,
+            C, c, F, f = self._full_inputs()
+            x, u, _, _ = solve_device_f64(f64(C), f64(c), f64(F), f64(f), f64(self.x_init), mask,
                                           self.T, self.n_state, self.n_ctrl, info=self._new_info())
             return self._out(x), self._out(u)
         x, u, _, _ = solve_device(*self._dev_inputs(), self.T, self.n_state, self.n_ctrl,

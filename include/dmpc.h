@@ -374,6 +374,47 @@ int dmpc_il_loss(int N, int T, int B, int nu, const float *u, const float *us, c
 int dmpc_il_param_step(int kind, int n_sc, const float *dQ, const float *dp, float *params, float *ms, float *grad,
                        int enable_mask, float lr, float alpha, float eps, dmpc_stream_t stream);
 
+/* LQR with batch-shared C and F (csrc/lqr_shared.hpp).  Neither C nor F has a batch axis, so the quadratic
+ * half of the recursion (V_t, K_t, Quu_t, Qxu_t) is ONE sweep for the whole batch; the affine half (v_t / k_t, the rollout,
+ * the gradient's second solve and co-state sweeps) runs per trajectory on the shared blocks.  nx <= 32, nu <= 8, float32.
+ * `layout` says which axes each input has (no copy is ever made: an axis that is absent is read with stride 0):
+ *   C [ns,ns] or [T,ns,ns] (C_TIME);  F [nx,ns] or [T-1 or T,nx,ns] (F_TIME; only F[t], t < T-1 is read);
+ *   c [ns], [T,ns] (CVEC_TIME) or [T,B,ns] (CVEC_TIME | CVEC_BATCH);  f NULL, [nx], [T-1,nx] (FVEC_TIME) or [T-1,B,nx]
+ *   (FVEC_TIME | FVEC_BATCH).  A BATCH bit without its TIME bit, or an unknown bit, is DMPC_E_BADARG. */
+#define DMPC_SHARED_C_TIME 1u
+#define DMPC_SHARED_F_TIME 2u
+#define DMPC_SHARED_CVEC_TIME 4u
+#define DMPC_SHARED_CVEC_BATCH 8u
+#define DMPC_SHARED_FVEC_TIME 16u
+#define DMPC_SHARED_FVEC_BATCH 32u
+
+/* dmpc_lqr_shared_workspace_bytes: the solve's workspace.  Its first dmpc_lqr_shared_saved_bytes hold the shared blocks of
+ *   every step (and the sweep's DMPC_INFO_* flags), which the gradient reads back as `ws_saved`: keep them until then.
+ * dmpc_lqr_shared_grad_workspace_bytes: the gradient's own workspace (per-trajectory co-states, reduction partials).
+ * All three are 0 for a non-positive size and for a shape beyond 32 / 8. */
+size_t dmpc_lqr_shared_workspace_bytes(int T, int B, int nx, int nu);
+size_t dmpc_lqr_shared_saved_bytes(int T, int nx, int nu);
+size_t dmpc_lqr_shared_grad_workspace_bytes(int T, int B, int nx, int nu);
+
+/* The solve -> x [T,B,nx], u [T,B,nu].  Two launches: the sweep (one workgroup), then one lane per trajectory.
+ * info[b] (optional) = the sweep's flags (DMPC_INFO_SINGULAR: an exact zero pivot in Quu) | DMPC_INFO_NONFINITE.
+ * DMPC_E_BADARG (NULL, non-positive size, bad layout, a base pointer not 16-byte aligned), DMPC_E_UNSUPPORTED (nx > 32,
+ * nu > 8, T > 65535), DMPC_E_WORKSPACE: all before anything is launched. */
+int dmpc_lqr_shared_solve(int T, int B, int nx, int nu, uint32_t layout, const float *C, const float *c, const float *F,
+                          const float *f, const float *x_init, float *x_out, float *u_out, void *ws, size_t ws_bytes,
+                          int32_t *info, dmpc_stream_t stream);
+
+/* DiffLqr.backward (differentiable_lqr.py:78-142) of a shared solve: C, c, F and `layout` as given to the solve, x, u its
+ * solution, ws_saved the front of its workspace (the shared blocks; C and F themselves are not read again).  Each gradient
+ * has its input's own shape: dC [ns,ns] / [T,ns,ns], dF [nx,ns] / [T-1,nx,ns], dc and df as c and f (reduced over the batch
+ * on the device where the input has no batch axis, over t where it has no time axis); d_x_init [B,nx].  dC, dF, df may be
+ * NULL (df must be NULL when the solve had no f).  Reductions are deterministic: partial sums in a fixed order, added in
+ * a fixed order by a second launch; no atomics.  strict_math as dmpc_lqr_kkt_grad. */
+int dmpc_lqr_shared_kkt_grad(int T, int B, int nx, int nu, uint32_t layout, const float *C, const float *c, const float *F,
+                             const float *x, const float *u, const void *ws_saved, const float *grad_x,
+                             const float *grad_u, int strict_math, float *d_x_init, float *dC, float *dc, float *dF,
+                             float *df, void *ws, size_t ws_bytes, int32_t *info, dmpc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,39 @@ int main() {
         if (wsb > 0) EXPECT(dmpc_lqr_solve(T, B, nx, nu, p, p, p, p, p, nullptr, nullptr, nullptr, p, p, ws, wsb - 1, pi, nullptr) == DMPC_E_WORKSPACE);
       }
   }
+  // batch-shared C and F: workspace queries, every layout, argument and workspace checks, the host path of both launches
+  for (int nx : {1, 3, 8, 17, 32, 33})
+    for (int nu : {1, 2, 5, 8, 9})
+      for (int T : {1, 2, 50})
+        for (int B : {1, 65, 4096}) {
+          const size_t wsb = dmpc_lqr_shared_workspace_bytes(T, B, nx, nu);
+          const size_t gwb = dmpc_lqr_shared_grad_workspace_bytes(T, B, nx, nu);
+          const bool ok = nx <= 32 && nu <= 8;
+          EXPECT(ok == (wsb > 0) && ok == (gwb > 0));
+          if (!ok) {
+            EXPECT(dmpc_lqr_shared_solve(T, B, nx, nu, 0, p, p, p, nullptr, p, p, p, ws, 1 << 30, pi, nullptr) == DMPC_E_UNSUPPORTED);
+            continue;
+          }
+          EXPECT(wsb > dmpc_lqr_shared_saved_bytes(T, nx, nu) && wsb >= (size_t)T * B * nu * 4);
+          EXPECT(gwb >= (size_t)T * B * (3 * nx + nu) * 4);
+          for (uint32_t layout = 0; layout < 64; ++layout) {
+            const bool good = !((layout & DMPC_SHARED_CVEC_BATCH) && !(layout & DMPC_SHARED_CVEC_TIME)) &&
+                              !((layout & DMPC_SHARED_FVEC_BATCH) && !(layout & DMPC_SHARED_FVEC_TIME));
+            const int rs = dmpc_lqr_shared_solve(T, B, nx, nu, layout, p, p, p, p, p, p, p, ws, wsb, pi, nullptr);
+            const int rg = dmpc_lqr_shared_kkt_grad(T, B, nx, nu, layout, p, p, p, p, p, ws, p, p, layout & 1, p, p, p, p, p, ws,
+                                                    gwb, pi, nullptr);
+            if (!good) EXPECT(rs == DMPC_E_BADARG && rg == DMPC_E_BADARG);
+          }
+          EXPECT(dmpc_lqr_shared_solve(T, B, nx, nu, 64, p, p, p, p, p, p, p, ws, wsb, pi, nullptr) == DMPC_E_BADARG);
+          EXPECT(dmpc_lqr_shared_solve(T, B, nx, nu, 0, nullptr, p, p, p, p, p, p, ws, wsb, pi, nullptr) == DMPC_E_BADARG);
+          EXPECT(dmpc_lqr_shared_solve(T, B, nx, nu, 0, p + 1, p, p, p, p, p, p, ws, wsb, pi, nullptr) == DMPC_E_BADARG);
+          EXPECT(dmpc_lqr_shared_solve(T, B, nx, nu, 0, p, p, p, p, p, p, p, ws, wsb - 1, pi, nullptr) == DMPC_E_WORKSPACE);
+          EXPECT(dmpc_lqr_shared_kkt_grad(T, B, nx, nu, 0, p, p, p, p, p, ws, p, p, 0, p, p, nullptr, p, p, ws, gwb, pi, nullptr) ==
+                 DMPC_E_BADARG);
+          EXPECT(dmpc_lqr_shared_kkt_grad(T, B, nx, nu, 0, p, p, p, p, p, ws, p, p, 0, p, p, p, p, p, ws, gwb - 1, pi, nullptr) ==
+                 DMPC_E_WORKSPACE);
+        }
+  EXPECT(dmpc_lqr_shared_workspace_bytes(0, 1, 1, 1) == 0 && dmpc_lqr_shared_saved_bytes(0, 1, 1) == 0);
   EXPECT(dmpc_lqr_kernel_family(0, 3) == DMPC_E_UNSUPPORTED);
   EXPECT(dmpc_lqr_workspace_bytes(0, 1, 1, 1) == 0);
   EXPECT(dmpc_lqr_solve(0, 1, 1, 1, p, p, p, p, p, nullptr, nullptr, nullptr, p, p, nullptr, 0, nullptr, nullptr) == DMPC_E_BADARG);
