@@ -80,6 +80,9 @@ SIGNATURES = {
     "dmpc_lqr_shared_solve": (_c_i, [_c_i] * 4 + [ctypes.c_uint32] + [_c_f] * 8 + [_c_sz, _c_f, _c_f]),
     "dmpc_lqr_shared_kkt_grad": (_c_i, [_c_i] * 4 + [ctypes.c_uint32] + [_c_f] * 8 + [_c_i] + [_c_f] * 6
                                  + [_c_sz, _c_f, _c_f]),
+    "dmpc_mpc_step_shared_grad_workspace_bytes": (_c_sz, [_c_i] * 4),
+    "dmpc_mpc_step_backward_shared": (_c_i, [_c_i] * 4 + [ctypes.c_uint32] + [_c_f] * 9 + [_c_f] * 5
+                                      + [_c_f, _c_f, ctypes.c_float] + [_c_f, _c_sz, _c_f, _c_f]),
 }
 
 _lib = None

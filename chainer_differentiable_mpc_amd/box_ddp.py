@@ -18,8 +18,8 @@ import torch
 from . import _lib
 from .approximate import approximate_cost, linearize_dynamics
 from .lqr_recursion import _as_tensor, _device_of, _workspace
-from .mpc_step import MPCstep, _MPCstepTiledFn
-from .util import LinDx, QuadCost, TiledQuadCost, get_cost, get_traj
+from .mpc_step import MPCstep, _MPCstepTiledDxFn, _MPCstepTiledFn
+from .util import LinDx, QuadCost, TiledLinDx, TiledQuadCost, get_cost, get_traj
 
 
 _UNRESOLVED = []     # solvers whose device loop has not been read back yet (lazy_status)
@@ -346,6 +346,9 @@ class BoxDDP(torch.nn.Module):
         if torch.is_grad_enabled() and (xi.requires_grad or Cc.requires_grad or cc.requires_grad or (
                 isinstance(dy, LinDx) and (dy.F.requires_grad or (dy.f is not None and dy.f.requires_grad)))):
             return None
+        if torch.is_grad_enabled() and isinstance(dy, TiledLinDx) and (dy.AB.requires_grad or (
+                dy.f0 is not None and dy.f0.requires_grad)):
+            return None       # (its leaves are AB / f0, not the detached tiles: every call of a training loop gets its gradient node)
         if params is not None:
             g_, m_, l_ = dy.host_params()
             if params != tuple((ctypes.c_float * 6)(g_, m_, l_, float(dy.dt), float(dy.max_torque), 1.0 if dy.clamp_grad_closed else 0.0)):
@@ -500,7 +503,8 @@ class BoxDDP(torch.nn.Module):
         tiled = isinstance(cost, TiledQuadCost) and not self.update_dynamics    # the gradient goes to (Q, p) alone
         if isinstance(cost, QuadCost) and (fused or isinstance(dynamics, LinDx)):
             leaves = [x_init] + ([cost.Q, cost.p] if isinstance(cost, TiledQuadCost) else [cost.C, cost.c]) + \
-                ([dynamics.F, dynamics.f] if isinstance(dynamics, LinDx) else [])
+                ([dynamics.AB, dynamics.f0] if isinstance(dynamics, TiledLinDx) else
+                 [dynamics.F, dynamics.f] if isinstance(dynamics, LinDx) else [])
         if not torch.is_grad_enabled() or (leaves is not None and not any(
                 isinstance(t, torch.Tensor) and t.requires_grad for t in leaves)):
             if self.detach_unconverged:
@@ -538,6 +542,30 @@ class BoxDDP(torch.nn.Module):
                 elif unconverged():
                     self._warn()
             return x, u, costs
+        if isinstance(dynamics, TiledLinDx) and self.update_dynamics:
+            AB, f0 = dynamics.AB, dynamics.f0
+            if last_norm is not None and x.is_cuda and isinstance(cost, QuadCost) and \
+                    _lib.load().dmpc_mpc_step_shared_grad_workspace_bytes(T, B, nx, nu) != 0:
+                # One [A|B] tiled over the batch, solved by the device loop: the node's inputs are the un-tiled tensors, its
+                # backward returns the gradient summed on the device in a fixed order (no dC, no [T-1,B,nx,ns] gradient), and
+                # the detach mask of :263-289 gates the incoming gradient there from the loop's own device flags - as the tiled
+                # cost above, so this solve too needs no host decision
+                d = x.device
+                retained = dict(C=_lib.f32c(Cm, d), c=_lib.f32c(cm, d), F=_lib.f32c(dynamics.F, d), x=_lib.f32c(x, d),
+                                u=_lib.f32c(u, d))
+                detach = (_lib.f32c(last_norm, d), self._loop_flag, self.eps) if self.detach_unconverged else None
+                spec = (T, B, nx, nu, d, _lib.f32c(lo, d), _lib.f32c(hi, d), detach)
+                x, u = _MPCstepTiledDxFn.apply(x[0].detach(), AB, f0, spec, retained, x, u)
+                if self.detach_unconverged:
+                    if deferred:
+                        self.__dict__["_warn_unconverged"] = True
+                    elif unconverged():
+                        self._warn()
+                return x, u, costs
+            # host loop / CPU tensors / a size the reduction does not serve: tile (AB, f0) ON the graph - TiledLinDx.F / .f are
+            # detached copies, the learnable tensors are AB and f0 - and take the generic node
+            Fm = TiledLinDx.tile(AB, 2, T, B)
+            fm = None if dynamics.f is None else (dynamics.f if f0 is None else TiledLinDx.tile(f0, 1, T, B))
         node = MPCstep(controls=u, T=T, u_upper=hi, u_lower=lo, n_batch=B, n_state=nx, n_ctrl=nu, current_states=x,
                        true_cost=detached_cost(), true_dynamics=detached_dyn(), ls_decay=self.ls_decay,
                        max_ls_iter=self.max_ls_iter, verbose=self.ilqr_verbose, need_expand=True, no_op_forward=True)

@@ -50,4 +50,17 @@ int lqr_second_solve(int T, int B, int nx, int nu, const float *C, const float *
                      const float *Ks, const float *Quu, const float *Qxu, float *x_out, float *u_out, int32_t *info,
                      hipStream_t stream);
 
+// lqr_shared_api.hip: the fixed-order reduction of parameter-shaped gradients (lqr_shared.hpp 3b, 3c) for another caller's
+// tau = (x, u), d_tau = (dtx, dtu) at their row strides, lambda, d_lambda [T,B,nx]: out_sign * the strict / non-strict forms
+bool shared_reduce_supported(int T, int nx, int nu);
+size_t shared_reduce_part_bytes(int T, int B, int nx, int nu);
+int shared_grad_reduce(int T, int B, int nx, int nu, uint32_t layout, int strict_math, float out_sign, const float *x,
+                       const float *u, const float *dtx, const float *dtu, int dtx_stride, int dtu_stride, const float *lam,
+                       const float *dlam, float *part, float *dC, float *dc, float *dF, float *df, hipStream_t stream);
+// mpc_api.hip: MPCstep.backward's first launch - the active set of u, -[grad_x; grad_u] behind BoxDDP's detach gate, x_init = 0
+void launch_active_mask(int T, int B, int nx, int nu, const float *u, const float *u_lower, const float *u_upper,
+                        const float *grad_x, const float *grad_u, uint8_t *mask, float *neg, float *x0, float *zero_a,
+                        float *zero_b, const float *detach_norm, const int32_t *detach_flag, float detach_eps,
+                        hipStream_t stream);
+
 }  // namespace dmpc

@@ -23,6 +23,10 @@ struct CostateArgs {
   // timesteps, one atomic add per element and wavefront; the caller zeroes them.  dC / dc may then be nullptr.
   float *dC_sum = nullptr, *dc_sum = nullptr;
   int nx_log = 0, nu_log = 0;   // container launches (costate_kernel<..., PAD>): the problem's own dimensions
+  // The co-state rows themselves, [T,B,nx] each: lambda_t and d_lambda_t as the recursion holds them (BEFORE out_sign), written
+  // by the lanes that hold them - what a reduction over the batch needs to form parameter-shaped dF / df without the dense
+  // ones (lqr_shared_reduce_kernel; dmpc_mpc_step_backward_shared).  dC, dc, dF, df may then all be nullptr.
+  float *lam_out = nullptr, *dlam_out = nullptr;
 };
 
 // Shape dispatch (defined in kkt_api.hip).

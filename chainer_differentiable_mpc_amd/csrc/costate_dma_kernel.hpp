@@ -187,6 +187,8 @@ __global__ __launch_bounds__(256) void costate_dma_kernel(const CostateArgs a) {
     lam = nl;
     dlam = ndl;
     if (a.df != nullptr && a.df_shift == 0 && t < T - 1 && is_x) a.df[tb * NX + lane] = a.out_sign * dlam;
+    if (a.lam_out != nullptr && is_x) a.lam_out[tb * NX + lane] = lam;
+    if (a.dlam_out != nullptr && is_x) a.dlam_out[tb * NX + lane] = dlam;
   };
 
   // Software pipeline of lqr_dma_kernel: at step t the DMA for step t - DB goes into the slot whose contents went to

@@ -145,6 +145,8 @@ __global__ __launch_bounds__(256) void costate_kernel(const CostateArgs a) {
     lam = (!PAD || is_x) ? nl : 0.f;
     dlam = (!PAD || is_x) ? ndl : 0.f;
     if (a.df != nullptr && a.df_shift == 0 && t < T - 1 && live && is_x) a.df[tb * nx + lane] = a.out_sign * dlam;
+    if (a.lam_out != nullptr && live && is_x) a.lam_out[tb * nx + lane] = lam;
+    if (a.dlam_out != nullptr && live && is_x) a.dlam_out[tb * nx + lane] = dlam;
   };
 
   Slot sa, sb, sc;  // two steps of loads in flight
@@ -226,6 +228,8 @@ __global__ __launch_bounds__(64) void costate_generic_kernel(const CostateArgs a
       lam[i] = nlam[i];
       dlam[i] = ndlam[i];
       if (a.df != nullptr && a.df_shift == 0 && t < T - 1) a.df[tb * nx + i] = a.out_sign * dlam[i];
+      if (a.lam_out != nullptr) a.lam_out[tb * nx + i] = lam[i];
+      if (a.dlam_out != nullptr) a.dlam_out[tb * nx + i] = dlam[i];
     }
     __syncthreads();
   }

@@ -140,6 +140,8 @@ __global__ __launch_bounds__(64) void costate_staged_kernel(const CostateArgs a,
     lam = is_x ? nl : 0.f;
     dlam = is_x ? ndl : 0.f;
     if (a.df != nullptr && a.df_shift == 0 && t < T - 1 && is_x) a.df[tb * nx + lane] = a.out_sign * dlam;
+    if (a.lam_out != nullptr && is_x) a.lam_out[tb * nx + lane] = lam;      // (left out of the counted wait, as dc / df are)
+    if (a.dlam_out != nullptr && is_x) a.dlam_out[tb * nx + lane] = dlam;
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the fetches past t = 0 have landed before the LDS goes back)
   if (a.dx0 != nullptr && is_x) a.dx0[(size_t)b * nx + lane] = a.out_sign * dlam;

@@ -253,6 +253,8 @@ __global__ __launch_bounds__(64 * WPB) void costate_wide_kernel(const CostateArg
     lam = nl + nl2;
     dlam = ndl + ndl2;
     if (a.df != nullptr && a.df_shift == 0 && t < T - 1 && is_x) a.df[tb * nx + lane] = a.out_sign * dlam;
+    if (a.lam_out != nullptr && is_x) a.lam_out[tb * nx + lane] = lam;
+    if (a.dlam_out != nullptr && is_x) a.dlam_out[tb * nx + lane] = dlam;
   };
 
   // ONE register set (lqr_wide_kernel.hpp): the slot of step t is waited for and read, then - once the reads are in -

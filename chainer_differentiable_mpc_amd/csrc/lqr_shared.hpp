@@ -548,10 +548,12 @@ __global__ __launch_bounds__(kSharedLaneThreads) void lqr_shared_grad_lane_kerne
 // 3b. Partial sums over a chunk of trajectories, step t = blockIdx.y, chunk blockIdx.x.  Thread (I, J, g): the 4x4 blocks
 // (I, J) of dC_t and (I < nx/4) dF_t over the trajectories g, g + G, ... of each tile; J = 0 also the 4-blocks I of dc_t,
 // df_t.  Record [t][chunk][g][shared_part_floats]: dC [ns][ns], dF [nx][ns], dc [ns], df [nx].
+// d_tau comes as two arrays with a row stride each: (dtau, dtau + nx) at stride ns for the shared LQR's one [T][B][ns] array,
+// (dx, du) at strides (nx, nu) for the MPC step's workspace (dmpc_mpc_step_backward_shared).
 __global__ __launch_bounds__(kSharedRedThreads) void lqr_shared_reduce_kernel(
     int T, int B, int nx, int nu, int strict_math, const float *__restrict__ x, const float *__restrict__ u,
-    const float *__restrict__ dtau, const float *__restrict__ lam, const float *__restrict__ dlam,
-    float *__restrict__ part) {
+    const float *__restrict__ dtx, const float *__restrict__ dtu, int dtx_stride, int dtu_stride,
+    const float *__restrict__ lam, const float *__restrict__ dlam, float *__restrict__ part) {
   constexpr int MS4 = shared_round4(kSharedMaxNx + kSharedMaxNu), MX4 = kSharedMaxNx, TB = kSharedRedTile;
   __shared__ __align__(16) float sTau[TB * MS4], sDtau[TB * MS4], sLam[TB * MX4], sDlam[TB * MX4], sDf[TB * MX4];
   const int ch = blockIdx.x, t = blockIdx.y, nchunk = gridDim.x;
@@ -575,7 +577,7 @@ __global__ __launch_bounds__(kSharedRedThreads) void lqr_shared_reduce_kernel(
       if (bb < nb && i < ns) {
         const size_t row = (size_t)t * B + b0 + bb;
         tv = i < nx ? x[row * nx + i] : u[row * nu + i - nx];
-        dv = dtau[row * ns + i];
+        dv = i < nx ? dtx[row * dtx_stride + i] : dtu[row * dtu_stride + i - nx];
       }
       sTau[bb * MS4 + i] = tv;
       sDtau[bb * MS4 + i] = dv;
@@ -651,9 +653,10 @@ __global__ __launch_bounds__(kSharedRedThreads) void lqr_shared_reduce_kernel(
 
 // 3c. The reduced gradients: one workgroup per output element; thread k adds the partial records k, k + 256, ... (over
 // chunks, groups and - where the input has no time axis - steps), then a tree in LDS: a fixed order, no atomics.
+// out_sign: +1 DiffLqr, -1 MPCstep (mpc/mpc_step.py:383-446 is minus the strict_math forms); times 1 changes no bit.
 constexpr int kSharedFinThreads = 256;
 __global__ __launch_bounds__(kSharedFinThreads) void lqr_shared_finalize_kernel(int T, int nx, int nu, uint32_t layout,
-                                                                                int nchunk, int G,
+                                                                                int nchunk, int G, float out_sign,
                                                                                 const float *__restrict__ part,
                                                                                 float *__restrict__ dC, float *__restrict__ dc,
                                                                                 float *__restrict__ dF, float *__restrict__ df) {
@@ -696,7 +699,7 @@ __global__ __launch_bounds__(kSharedFinThreads) void lqr_shared_finalize_kernel(
       if (tid < h) red[tid] += red[tid + h];
       __syncthreads();
     }
-    if (tid == 0) out[r] = red[0];
+    if (tid == 0) out[r] = out_sign * red[0];
     __syncthreads();
   }
 }

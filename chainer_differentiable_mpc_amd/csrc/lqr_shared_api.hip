@@ -38,7 +38,7 @@ GradWs grad_ws(int T, int B, int nx, int nu) {
   g.lam = g.dtau + round_up(tb * (nx + nu) * sizeof(float), 256);
   g.dlam = g.lam + round_up(tb * nx * sizeof(float), 256);
   g.part = g.dlam + round_up(tb * nx * sizeof(float), 256);
-  g.total = g.part + (size_t)T * n_chunks(B) * shared_red_groups(nx, nu) * shared_part_floats(nx, nu) * sizeof(float);
+  g.total = g.part + shared_reduce_part_bytes(T, B, nx, nu);
   return g;
 }
 
@@ -83,6 +83,31 @@ struct GradLane {
 };
 
 }  // namespace
+
+namespace dmpc {
+
+bool shared_reduce_supported(int T, int nx, int nu) { return shape_supported(T, nx, nu); }
+
+size_t shared_reduce_part_bytes(int T, int B, int nx, int nu) {
+  return (size_t)T * n_chunks(B) * shared_red_groups(nx, nu) * shared_part_floats(nx, nu) * sizeof(float);
+}
+
+// partial sums per (step, chunk, thread group), then the fixed-order sum of the partials: out_sign * (the reduce kernel's forms)
+int shared_grad_reduce(int T, int B, int nx, int nu, uint32_t layout, int strict_math, float out_sign, const float *x,
+                       const float *u, const float *dtx, const float *dtu, int dtx_stride, int dtu_stride, const float *lam,
+                       const float *dlam, float *part, float *dC, float *dc, float *dF, float *df, hipStream_t stream) {
+  const int nchunk = n_chunks(B), G = shared_red_groups(nx, nu);
+  DMPC_LAUNCH_GGL(lqr_shared_reduce_kernel, dim3(nchunk, T), dim3(kSharedRedThreads), 0, stream, T, B, nx, nu, strict_math, x,
+                  u, dtx, dtu, dtx_stride, dtu_stride, lam, dlam, part);
+  const long long outs = (long long)(nx + nu) * (nx + nu) * T + (long long)nx * (nx + nu) * T + (long long)(nx + nu) * T +
+                         (long long)nx * T;
+  const int grid = (int)(outs < 65536 ? outs : 65536);
+  DMPC_LAUNCH_GGL(lqr_shared_finalize_kernel, dim3(grid), dim3(kSharedFinThreads), 0, stream, T, nx, nu, layout, nchunk, G,
+                  out_sign, (const float *)part, dC, dc, dF, df);
+  return (int)hipGetLastError();
+}
+
+}  // namespace dmpc
 
 extern "C" {
 
@@ -145,16 +170,9 @@ int dmpc_lqr_shared_kkt_grad(int T, int B, int nx, int nu, uint32_t layout, cons
   by_size<GradLane>(nx, nu, T, B, nx, nu, layout, strict_math ? 1 : 0, c, x, u, grad_x, grad_u,
                     static_cast<const float *>(ws_saved), reinterpret_cast<float *>(w + g.kbuf), dtau, lam, dlam, d_x_init,
                     fB ? df : nullptr, info, stream);
-  const int nchunk = n_chunks(B), G = shared_red_groups(nx, nu);
-  DMPC_LAUNCH_GGL(lqr_shared_reduce_kernel, dim3(nchunk, T), dim3(kSharedRedThreads), 0, stream, T, B, nx, nu,
-                  strict_math ? 1 : 0, x, u, (const float *)dtau, (const float *)lam, (const float *)dlam, part);
   float *dc_red = cB ? nullptr : dc, *df_red = fB ? nullptr : df;
-  const long long outs = (long long)(nx + nu) * (nx + nu) * T + (long long)nx * (nx + nu) * T + (long long)(nx + nu) * T +
-                         (long long)nx * T;
-  const int grid = (int)(outs < 65536 ? outs : 65536);
-  DMPC_LAUNCH_GGL(lqr_shared_finalize_kernel, dim3(grid), dim3(kSharedFinThreads), 0, stream, T, nx, nu, layout, nchunk, G,
-                  (const float *)part, dC, dc_red, dF, df_red);
-  return (int)hipGetLastError();
+  return shared_grad_reduce(T, B, nx, nu, layout, strict_math ? 1 : 0, 1.0f, x, u, dtau, dtau + nx, nx + nu, nx + nu, lam, dlam,
+                            part, dC, dc_red, dF, df_red, stream);
 }
 
 }  // extern "C"

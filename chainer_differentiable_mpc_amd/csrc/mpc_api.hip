@@ -633,6 +633,16 @@ static int grid_for(size_t n) {
   return (int)(blocks > 8192 ? 8192 : (blocks == 0 ? 1 : blocks));
 }
 
+void launch_active_mask(int T, int B, int nx, int nu, const float *u, const float *u_lower, const float *u_upper,
+                        const float *grad_x, const float *grad_u, uint8_t *mask, float *neg, float *x0, float *zero_a,
+                        float *zero_b, const float *detach_norm, const int32_t *detach_flag, float detach_eps,
+                        hipStream_t stream) {
+  const size_t rows = (size_t)T * B;
+  DMPC_LAUNCH_GGL(active_mask_kernel, dim3(grid_for(rows * (nx + nu))), dim3(256), 0, stream, rows, nx, nu, u, u_lower,
+                  u_upper, grad_x, grad_u, mask, neg, x0, (size_t)B * nx, zero_a, zero_b, B, detach_norm, detach_flag,
+                  detach_eps);
+}
+
 }  // namespace dmpc
 
 using namespace dmpc;
@@ -1000,10 +1010,8 @@ int dmpc_mpc_step_backward(int T, int B, int nx, int nu, const float *C_hat, con
   float *dx = reinterpret_cast<float *>(base + w.dx);
   float *du = reinterpret_cast<float *>(base + w.du);
   uint8_t *mask = reinterpret_cast<uint8_t *>(base + w.mask);
-  const size_t rows = (size_t)T * B;
-  DMPC_LAUNCH_GGL(active_mask_kernel, dim3(grid_for(rows * (nx + nu))), dim3(256), 0, stream, rows, nx, nu, u,
-                     u_lower, u_upper, grad_x, grad_u, mask, neg, x0, (size_t)B * nx, dC_sum, dc_sum, B, detach_norm,
-                     detach_flag, detach_eps);
+  launch_active_mask(T, B, nx, nu, u, u_lower, u_upper, grad_x, grad_u, mask, neg, x0, dC_sum, dc_sum, detach_norm, detach_flag,
+                     detach_eps, stream);
   // LQR_active(0, C, -d_tau, F, None, u_zero_Index=active)                               mpc_step.py:374-376
   int rc = dmpc_lqr_solve(T, B, nx, nu, C_hat, neg, F_hat, nullptr, x0, mask, nullptr, nullptr, dx, du,
                           base + w.lqr, w.total - w.lqr, info, stream_);

@@ -27,6 +27,7 @@ import torch
 
 from . import _lib
 from .lqr_recursion import _as_tensor, _device_of, _workspace, raise_info
+from .lqr_shared import SHARED_F_TIME, SHARED_FVEC_TIME
 from .util import LinDx, QuadCost, bdot, bmv, bquad, clamp, get_cost
 
 LqrBackOut = namedtuple("lqrBackOut", "n_total_qp_iter")
@@ -175,6 +176,66 @@ class _MPCstepTiledFn(torch.autograd.Function):
         xd, xdev, qd, qdev = ctx.meta
         return (dx0.to(device=xdev, dtype=xd) if ctx.need_x0 else None, dQ.to(device=qdev, dtype=qd),
                 dp.to(device=qdev, dtype=qd), None, None, None, None)
+
+
+def tiled_dynamics_gradient(T, B, nx, nu, dev, r, lo, hi, gx, gu, detach=None, time_axis=False, want_df=False,
+                            f_time_axis=False):
+    """`MPCstep.backward` (mpc_step.py:330-460) for dynamics that are one [A|B] (and f) tiled over the batch: -> (dx_init
+    [B,nx], dAB, df0 | None) with dAB = sum_{t,b} dF [nx,ns] (time_axis: sum_b dF [T-1,nx,ns]) and df0 = sum df [nx]
+    (f_time_axis: [T-1,nx]) when want_df; the co-state kernel writes its rows only and the sums are formed in a fixed order
+    (`dmpc_mpc_step_backward_shared`): no dC, no dense dF, bit-reproducible.  r: retained float32 device tensors C, c, F
+    ([T-1 or T,B,nx,ns]), x, u; detach as in `tiled_cost_gradient`.  None where the entry point does not serve the size."""
+    lib = _lib.load()
+    ns = nx + nu
+    need = lib.dmpc_mpc_step_shared_grad_workspace_bytes(T, B, nx, nu)
+    if need == 0:
+        return None
+    n_F = ((T - 1) if time_axis else 1) * nx * ns
+    n_f = (((T - 1) if f_time_axis else 1) * nx) if want_df else 0
+    out = torch.empty((B * nx + n_F + n_f,), dtype=torch.float32, device=dev)      # one allocation
+    dx0 = out[:B * nx].view(B, nx)
+    dAB = out[B * nx:B * nx + n_F].view((T - 1, nx, ns) if time_axis else (nx, ns))
+    df0 = out[B * nx + n_F:].view((T - 1, nx) if f_time_axis else (nx,)) if want_df else None
+    layout = (SHARED_F_TIME if time_axis else 0) | (SHARED_FVEC_TIME if (want_df and f_time_axis) else 0)
+    ws = _workspace(need, dev)
+    dn, dfl, de = (None, None, 0.0) if detach is None else (detach[0], detach[1], float(detach[2]))
+    with _lib.guard(dev):
+        rc = lib.dmpc_mpc_step_backward_shared(T, B, nx, nu, layout, _lib.ptr(r["C"]), _lib.ptr(r["c"]), _lib.ptr(r["F"]),
+                                               _lib.ptr(r["x"]), _lib.ptr(r["u"]), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(gx),
+                                               _lib.ptr(gu), _lib.ptr(dx0), None, None, _lib.ptr(dAB), _lib.ptr(df0),
+                                               _lib.ptr(dn), _lib.ptr(dfl), de, _lib.ptr(ws), need, None, _lib.stream_ptr(dev))
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    _lib.check(rc, "dmpc_mpc_step_backward_shared")
+    return dx0, dAB, df0
+
+
+class _MPCstepTiledDxFn(torch.autograd.Function):
+    """The gradient node of `BoxDDP(update_dynamics=True)` for a `TiledLinDx` (no-op forward, mpc/box_ddp.py:247-259): inputs
+    are the un-tiled (AB, f0); backward returns the gradient summed over the batch (and time), as the backward of the tiling
+    would (`tiled_dynamics_gradient`); the cost is a constant of this node (:252-258).  `spec` as `_MPCstepTiledFn`'s."""
+
+    @staticmethod
+    def forward(ctx, x_init, AB, f0, spec, retained, x_best, u_best):
+        ctx.spec, ctx.retained = spec, retained
+        ctx.meta = (x_init.dtype, x_init.device, AB.dtype, AB.device, AB.dim() == 3,
+                    None if f0 is None else (f0.dtype, f0.device, f0.dim() == 2))
+        ctx.need_x0 = x_init.requires_grad
+        return x_best.detach(), u_best.detach()
+
+    @staticmethod
+    def backward(ctx, dl_dx, dl_du):
+        T, B, nx, nu, dev, lo, hi, detach = ctx.spec
+        xd, xdev, ad, adev, a_time, fmeta = ctx.meta
+        gx = None if dl_dx is None else _lib.f32c(dl_dx, dev)
+        gu = None if dl_du is None else _lib.f32c(dl_du, dev)
+        got = tiled_dynamics_gradient(T, B, nx, nu, dev, ctx.retained, lo, hi, gx, gu, detach, time_axis=a_time,
+                                      want_df=fmeta is not None, f_time_axis=fmeta is not None and fmeta[2])
+        if got is None:       # (BoxDDP asks for the size before it builds this node)
+            raise _lib.DmpcError("dmpc_mpc_step_backward_shared does not serve (nx, nu) = (%d, %d)" % (nx, nu))
+        dx0, dAB, df0 = got
+        return (dx0.to(device=xdev, dtype=xd) if ctx.need_x0 else None, dAB.to(device=adev, dtype=ad),
+                None if fmeta is None else df0.to(device=fmeta[1], dtype=fmeta[0]), None, None, None, None)
 
 
 def tiled_gradient_inputs(out):

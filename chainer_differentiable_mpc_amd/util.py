@@ -39,6 +39,37 @@ class TiledQuadCost(QuadCost):
         return self
 
 
+class TiledLinDx(LinDx):
+    """A `LinDx` that is ONE [A|B] tiled over the batch (and over time) - the learnable dynamics of mpc/mpc_net.py, which
+    builds its model with `expand_time_batch`.  `.F` / `.f` are the dense, detached, contiguous tiles the forward kernels
+    read ([T-1,B,nx,ns], [T-1,B,nx] or None); `.AB` ([nx,ns] or [T-1,nx,ns]) and `.f0` ([nx], [T-1,nx] or None) the tensors
+    a gradient flows to: `BoxDDP(update_dynamics=True)` then asks for the gradient already summed over the batch (and time)
+    on the device (`mpc_step.tiled_dynamics_gradient`) instead of forming dF [T-1,B,nx,ns] and leaving the sum to autograd's
+    backward of the tiling.  Everything that takes a `LinDx` takes it."""
+
+    def __new__(cls, AB, f, T, n_batch):
+        F = cls.tile(AB.detach(), 2, T, n_batch).contiguous()
+        ft = None if f is None else cls.tile(f.detach(), 1, T, n_batch).contiguous()
+        return cls.from_tiles(F, ft, AB, f)
+
+    @classmethod
+    def from_tiles(cls, F, f, AB, f0):
+        """around tiles the caller already holds (F [T-1,B,nx,ns], f [T-1,B,nx] or None, equal to AB, f0 repeated): no copy,
+        so a solver called again sees the same buffers (`MpcNet_dx(shared=True)` refreshes them in place)"""
+        self = super().__new__(cls, F, f)
+        self.AB, self.f0 = AB, f0
+        return self
+
+    @staticmethod
+    def tile(m, base_dim, T, n_batch):
+        """m without a time axis (m.dim() == base_dim) or with one -> the view [T-1, n_batch, ...] (on m's graph)"""
+        assert m.dim() in (base_dim, base_dim + 1), "a tiled model is [...] or [T-1, ...]"
+        if m.dim() == base_dim:
+            return expand_time_batch(m, T - 1, n_batch)
+        assert m.shape[0] == T - 1, "a tiled model with a time axis has T-1 slices"
+        return m.unsqueeze(1).expand((T - 1, n_batch) + tuple(m.shape[1:]))
+
+
 def bmv(a, x):
     assert a.shape[0] == x.shape[0], "batch mismatch"
     assert a.shape[2] == x.shape[1], "mat mul dim mismatch"

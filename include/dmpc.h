@@ -415,6 +415,23 @@ int dmpc_lqr_shared_kkt_grad(int T, int B, int nx, int nu, uint32_t layout, cons
                              const float *grad_u, int strict_math, float *d_x_init, float *dC, float *dc, float *dF,
                              float *df, void *ws, size_t ws_bytes, int32_t *info, dmpc_stream_t stream);
 
+/* MPCstep.backward (mpc_step.py:330-460) for a model that is ONE set of parameters tiled over the batch - mpc/mpc_net.py's
+ * learnable [A|B].  Inputs are dmpc_mpc_step_backward's: the dense C_hat [T,B,ns,ns], c_hat [T,B,ns],
+ * F_hat [T-1,B,nx,ns] the solve read, its x, u, the box, the incoming gradients and the detach gate.  Outputs have the
+ * PARAMETER's shape, summed over the batch on the device (and over t where the `layout` bit is clear; only the four *_TIME
+ * bits are taken, a *_BATCH bit is DMPC_E_BADARG): dC [ns,ns] / [T,ns,ns], dc [ns] / [T,ns], dF [nx,ns] / [T-1,nx,ns],
+ * df [nx] / [T-1,nx], with the reference's signs; each may be NULL and is then not formed.  d_x_init [B,nx] is always
+ * written.  Five launches and the active-set LQR solve: the co-state kernel writes its rows lambda_t, d_lambda_t into the
+ * workspace instead of dense dC / dF, then the shared LQR's two reduction launches add them in a fixed order - no atomics,
+ * bit-reproducible, no host synchronisation and no allocation (it can be recorded in a hipGraph), any B >= 1.
+ * DMPC_E_UNSUPPORTED (nothing launched) for nx > 32, nu > 8 or T > 65535; the workspace size is 0 for those. */
+size_t dmpc_mpc_step_shared_grad_workspace_bytes(int T, int B, int nx, int nu);
+int dmpc_mpc_step_backward_shared(int T, int B, int nx, int nu, uint32_t layout, const float *C_hat, const float *c_hat,
+                                  const float *F_hat, const float *x, const float *u, const float *u_lower,
+                                  const float *u_upper, const float *grad_x, const float *grad_u, float *d_x_init, float *dC,
+                                  float *dc, float *dF, float *df, const float *detach_norm, const int32_t *detach_flag,
+                                  float detach_eps, void *ws, size_t ws_bytes, int32_t *info, dmpc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

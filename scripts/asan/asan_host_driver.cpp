@@ -70,6 +70,24 @@ int main() {
           const size_t gwb = dmpc_lqr_shared_grad_workspace_bytes(T, B, nx, nu);
           const bool ok = nx <= 32 && nu <= 8;
           EXPECT(ok == (wsb > 0) && ok == (gwb > 0));
+          {   // the MPC step's parameter-shaped gradient over the same reduction: workspace query, layouts, argument checks, host path
+            const size_t mwb = dmpc_mpc_step_shared_grad_workspace_bytes(T, B, nx, nu);
+            EXPECT((ok && T > 1) == (mwb > 0));
+            for (uint32_t layout = 0; layout < 64; ++layout) {
+              const int rm = dmpc_mpc_step_backward_shared(T, B, nx, nu, layout, p, p, p, p, p, p, p, p, p, p, layout & 1 ? p : nullptr,
+                                                           layout & 4 ? p : nullptr, p, layout & 16 ? p : nullptr, p, pi, 1e-5f, ws,
+                                                           mwb, pi, nullptr);
+              if (T <= 1 || (layout & (DMPC_SHARED_CVEC_BATCH | DMPC_SHARED_FVEC_BATCH))) EXPECT(rm == DMPC_E_BADARG);
+              else if (!ok) EXPECT(rm == DMPC_E_UNSUPPORTED);
+            }
+            if (mwb > 0) {
+              EXPECT(mwb >= (size_t)T * B * (4 * nx + 2 * nu) * 4 + dmpc_lqr_workspace_bytes(T, B, nx, nu));
+              EXPECT(dmpc_mpc_step_backward_shared(T, B, nx, nu, 0, p, p, nullptr, p, p, p, p, p, p, p, nullptr, nullptr, p, nullptr,
+                                                   nullptr, nullptr, 0.f, ws, mwb, pi, nullptr) == DMPC_E_BADARG);
+              EXPECT(dmpc_mpc_step_backward_shared(T, B, nx, nu, 0, p, p, p, p, p, p, p, p, p, p, nullptr, nullptr, p, nullptr,
+                                                   nullptr, nullptr, 0.f, ws, mwb - 1, pi, nullptr) == DMPC_E_WORKSPACE);
+            }
+          }
           if (!ok) {
             EXPECT(dmpc_lqr_shared_solve(T, B, nx, nu, 0, p, p, p, nullptr, p, p, p, ws, 1 << 30, pi, nullptr) == DMPC_E_UNSUPPORTED);
             continue;
