@@ -1,5 +1,5 @@
-// costate_args.hpp - argument block and shape dispatch of the co-state / outer-product kernel
-// (kernels in costate_kernels.hpp, instantiated once in kkt_api.hip; also called by mpc_api.hip).
+// costate_args.hpp - argument block and shape dispatch of the co-state / outer-product kernels (costate_kernels.hpp, _dma_,
+// _wide_, _staged_kernel.hpp; shared pieces: costate_common.hpp), instantiated once in kkt_api.hip; the MPC entry points call it too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,8 +31,9 @@ struct CostateArgs {
 
 // Shape dispatch (defined in kkt_api.hip).
 int launch_costate(int nx, int nu, const CostateArgs &a, hipStream_t stream);
-// dC_sum / dc_sum are formed by the LDS-DMA co-state kernel alone: does launch_costate take that kernel for this size?
-// (callers refuse the sums with DMPC_E_UNSUPPORTED otherwise - the other kernels would leave them untouched)
-bool costate_sums_available(int T, int B, int nx, int nu);
+// dC_sum / dc_sum are formed by the LDS-DMA 16-lane kernel alone: does launch_costate take that kernel for this size?
+// aligned: every array it moves in 16-byte chunks is (C, c, r, F, x, u, dx, du, dC, dF).  Callers refuse the sums with
+// DMPC_E_UNSUPPORTED otherwise, before they launch anything - as launch_costate itself does.
+bool costate_sums_available(int T, int B, int nx, int nu, bool aligned);
 
 }  // namespace dmpc

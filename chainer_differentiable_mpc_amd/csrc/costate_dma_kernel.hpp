@@ -8,8 +8,7 @@
 // Follows DiffLqr.backward, lqr/differentiable_lqr.py:85-134, and MPCstep.backward, mpc/mpc_step.py:383-446.
 #pragma once
 #include "costate_kernels.hpp"
-#include "dma_gather.hpp"
-#include "lqr_dma_kernel.hpp"
+#include "lqr_dma_kernel.hpp"   // wait_vmcnt
 
 namespace dmpc {
 
@@ -24,25 +23,14 @@ __device__ __forceinline__ void store_chunks(const float *scr, float *dst, int l
   }
 }
 
+// The ring layout (CostateRingLayout) of the 16-lane shapes: where a trajectory's nx * ns floats are whole chunks, the control
+// rows of C are not fetched (a fifth of C: 16 MB of 331 at the headline size).
+// Output staging: the wave's dC (dF) rows of one timestep are one contiguous run of HBM - they go through LDS so that the
+// stores are whole 16-byte chunks, 64 lanes wide, instead of 8-byte pieces 40 bytes apart.
 template <int NX, int NU, int DB>
-struct CostateDmaLayout {
-  static constexpr int NS = NX + NU;
-  // 16-byte chunks of one wave-step (four trajectories): [C | c | r | F | x | u | dx | du].  Only the state rows of C
-  // enter the co-state recursions (differentiable_lqr.py:92,102,115,124: C[:nx, :]): where a trajectory's nx * ns
-  // floats are whole chunks, the control rows are not fetched (a fifth of C: 16 MB of 331 at the headline size)
-  static constexpr bool kStateRowsOnly = (NX * NS) % 4 == 0;
-  static constexpr int kCRows = kStateRowsOnly ? NX : NS;       // rows of C_t per trajectory in the slot
-  static constexpr int nC = kCRows * NS, nc = NS, nF = NX * NS, nx_ = NX, nu_ = NU;
-  static constexpr int CH_C = 0, CH_c = CH_C + nC, CH_r = CH_c + nc, CH_F = CH_r + nc, CH_x = CH_F + nF;
-  static constexpr int CH_u = CH_x + nx_, CH_dx = CH_u + nu_, CH_du = CH_dx + nx_, CH_END = CH_du + nu_;
-  static constexpr int OFF_C = CH_C * 4, OFF_c = CH_c * 4, OFF_r = CH_r * 4, OFF_F = CH_F * 4, OFF_x = CH_x * 4;
-  static constexpr int OFF_u = CH_u * 4, OFF_dx = CH_dx * 4, OFF_du = CH_du * 4;   // in floats
-  static constexpr int kDma = (CH_END + 63) / 64;   // gather DMAs per step; padding lanes repeat chunk 0 of C
-  static constexpr int SLOT = kDma * 256;           // floats per wave and timestep (whole 1 KB pieces)
-  // output staging: the wave's dC (dF) rows of one timestep are one contiguous run of HBM - they go through LDS so that
-  // the stores are whole 16-byte chunks, 64 lanes wide, instead of 8-byte pieces 40 bytes apart
-  static constexpr int SCR = 4 * NS * NS + 4 * NX * NS;   // floats per wave
-  static constexpr size_t lds_bytes() { return (size_t)4 * (DB * SLOT + SCR) * 4; }
+struct CostateDmaLayout : CostateRingLayout<NX, NU, DB, (NX * (NX + NU)) % 4 == 0 ? NX : NX + NU,
+                                            4 * (NX + NU) * (NX + NU) + 4 * NX * (NX + NU)> {
+  static constexpr size_t lds_bytes() { return (size_t)4 * (DB * CostateDmaLayout::SLOT + CostateDmaLayout::SCR) * 4; }
 };
 
 template <int NX, int NU, int DB>
@@ -50,7 +38,6 @@ __global__ __launch_bounds__(256) void costate_dma_kernel(const CostateArgs a) {
   using Lay = CostateDmaLayout<NX, NU, DB>;
   constexpr int NS = NX + NU, L = 16;
   static_assert(NS <= L, "tau must fit the lane group");
-  static_assert((DB - 1) * Lay::kDma <= 63, "ring too deep for vmcnt");
   static_assert(DB % 2 == 0 && DB >= 2, "two alternating register sets");
   static_assert(Lay::kDma <= 8, "gather groups");
   using Blk = RiccatiBlocks<NX, NU, L>;
@@ -76,7 +63,7 @@ __global__ __launch_bounds__(256) void costate_dma_kernel(const CostateArgs a) {
   const bool is_tau = lane < NS;
   const int lane_x = is_x ? lane : NX - 1;  // clamped: rows/columns re-read by the idle lanes, never used
   const int lane_t = is_tau ? lane : NS - 1;
-  const float wa = 0.5f, wb = a.dC_mode == 0 ? 1.0f : 0.5f;
+  const float wa = kCostateWa, wb = costate_wb(a.dC_mode);
 
   // per-lane source pointers of the gather groups: chunk g = 64 q + lane64 of the slot.  Every array steps back by
   // one timestep per fetch; F has no slice T-1, so its lanes start at T-2 and sit out the first step.
@@ -93,7 +80,7 @@ __global__ __launch_bounds__(256) void costate_dma_kernel(const CostateArgs a) {
     size_t skip = 0;   // C, state rows only: trajectory k of the wave starts k * (ns - nx) * ns floats further on
     if (gg < Lay::CH_c) {
       base = (const char *)a.C; per = (size_t)NS * NS * 4; g0 = Lay::CH_C;
-      if constexpr (Lay::kStateRowsOnly) skip = (size_t)(gg / (NX * NS / 4)) * ((NS - NX) * NS * 4);
+      if constexpr (Lay::kCRows == NX) skip = (size_t)(gg / (NX * NS / 4)) * ((NS - NX) * NS * 4);
     }
     else if (gg < Lay::CH_r) { base = (const char *)a.c; per = (size_t)NS * 4; g0 = Lay::CH_c; }
     else if (gg < Lay::CH_F) {   // r: rows of r_cols floats - the chunks past the wave's 4 rows repeat its chunk 0
@@ -129,10 +116,7 @@ __global__ __launch_bounds__(256) void costate_dma_kernel(const CostateArgs a) {
   const int i_crow = Lay::OFF_C + (r * Lay::kCRows + lane_x) * NS;   // row lane_x of C_t
   const int i_c = Lay::OFF_c + r * NS + lane_x, i_r = Lay::OFF_r + r * rc + lane_x;
   const int i_fcol = Lay::OFF_F + r * NX * NS + lane_x;     // column lane_x of F_t[:, :NX]
-  struct Slot {
-    float tau, dtau, ci, ri;
-    float Crow[NS], Fcol[NX];
-  };
+  using Slot = CostateSlot<NX, NS>;
   auto read_slot = [&](const float *slot, Slot &s) {
     s.tau = slot[i_tau];
     s.dtau = slot[i_dtau];
@@ -162,7 +146,7 @@ __global__ __launch_bounds__(256) void costate_dma_kernel(const CostateArgs a) {
         }
         store_chunks<NX * NS>(scrF, a.dF + ((size_t)t * B + b0) * (NX * NS), lane64);
       }
-      if (a.df != nullptr && a.df_shift == 1 && is_x) a.df[tb * NX + lane] = a.out_sign * dlam;
+      costate_store_before(a, t, tb, NX, lane, is_x, lam, dlam);
     }
     if (a.dC != nullptr || summed) {                                          // :128-129
       float row[NS];
@@ -186,9 +170,7 @@ __global__ __launch_bounds__(256) void costate_dma_kernel(const CostateArgs a) {
     if (t < T - 1) Blk::dots2_nx(nl, ndl, s.Fcol, lam, dlam);
     lam = nl;
     dlam = ndl;
-    if (a.df != nullptr && a.df_shift == 0 && t < T - 1 && is_x) a.df[tb * NX + lane] = a.out_sign * dlam;
-    if (a.lam_out != nullptr && is_x) a.lam_out[tb * NX + lane] = lam;
-    if (a.dlam_out != nullptr && is_x) a.dlam_out[tb * NX + lane] = dlam;
+    costate_store_after(a, t, tb, NX, lane, is_x, lam, dlam);
   };
 
   // Software pipeline of lqr_dma_kernel: at step t the DMA for step t - DB goes into the slot whose contents went to

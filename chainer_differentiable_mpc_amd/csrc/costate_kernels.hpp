@@ -12,11 +12,8 @@
 //   dC_t row i (lane i < NS), dF_t row k (lane k < NX) are built with broadcast-multiplies and stored as
 //   contiguous rows.
 #pragma once
-#include "colwise.hpp"
-#include "costate_args.hpp"
-#include "dpp_blocks_gen.hpp"
+#include "costate_common.hpp"
 #include "lqr_kernels.hpp"
-#include "riccati_blocks.hpp"
 
 namespace dmpc {
 
@@ -43,7 +40,6 @@ __global__ __launch_bounds__(256) void costate_kernel(const CostateArgs a) {
   constexpr int NS = NX + NU;
   static_assert(NS <= L, "tau must fit the lane group");
   constexpr int GPB = 256 / L;
-  using G = Group<L>;
   using Blk = RiccatiBlocks<NX, NU, L>;  // fused DPP broadcast-FMA blocks for the 16-lane shapes (dpp_blocks_gen.hpp)
 
   const int lane = threadIdx.x % L;
@@ -61,17 +57,14 @@ __global__ __launch_bounds__(256) void costate_kernel(const CostateArgs a) {
   const bool is_tau = PAD ? lrow >= 0 : lane < NS;
   const int lane_x = is_x ? lane : nx - 1;    // clamped: rows/columns re-read by the idle lanes, never used
   const int lane_t = PAD ? (lrow >= 0 ? lrow : ns - 1) : (is_tau ? lane : NS - 1);   // index into [x; u]
-  const float wa = 0.5f, wb = a.dC_mode == 0 ? 1.0f : 0.5f;
+  const float wa = kCostateWa, wb = costate_wb(a.dC_mode);
 
   float lam = 0.f, dlam = 0.f;  // lambda_{t+1}[lane], d_lambda_{t+1}[lane]  (lanes < NX)
 
   // Inputs of one timestep.  With one wavefront per SIMD nothing else hides HBM latency, so the loads of step
   // t-2 are issued before step t is computed (three banks, statically rotated - hipcc drains vmcnt at a loop
   // header, so the prefetch has to sit in the same iteration as the compute it overlaps).
-  struct Slot {
-    float tau, dtau, ci, ri;
-    float Crow[NS], Fcol[NX];
-  };
+  using Slot = CostateSlot<NX, NS>;
   auto load = [&](int t, Slot &s) __attribute__((always_inline)) {
     t = t < 0 ? 0 : t;  // the prefetch past t = 0 re-reads step 0 (never consumed)
     const size_t tb = (size_t)t * B + b;
@@ -80,26 +73,20 @@ __global__ __launch_bounds__(256) void costate_kernel(const CostateArgs a) {
     const float *dp = lane_t < nx ? a.dx + tb * nx + lane_t : a.du + tb * nu + (lane_t - nx);
     s.tau = *tp;
     s.dtau = *dp;
+    const float *Cp = a.C + (tb * ns + lane_x) * ns;
     if constexpr (PAD) {   // clamped addresses; step() discards what lies outside the problem
-      const float *Cp = a.C + (tb * ns + lane_x) * ns;
       static_for<0, NS>([&](auto j) {
         const int lj = logical(j.value);
         s.Crow[j.value] = Cp[lj >= 0 ? lj : 0];
       });
-      s.ci = a.c[tb * ns + lane_x];
-      s.ri = a.r[tb * (a.r_cols ? a.r_cols : ns) + lane_x];
-      const int tF = t < T - 1 ? t : (T > 1 ? T - 2 : 0);
-      const float *Fp = (T > 1 ? a.F : a.C) + ((size_t)tF * B + b) * nx * ns + lane_x;
-      static_for<0, NX>([&](auto k) { s.Fcol[k.value] = Fp[(k.value < nx ? k.value : 0) * ns]; });
-      return;
+    } else {
+      load_contig<NS>(Cp, s.Crow);
     }
-    load_contig<NS>(a.C + (tb * NS + lane_x) * NS, s.Crow);
-    s.ci = a.c[tb * NS + lane_x];
-    s.ri = a.r[tb * (a.r_cols ? a.r_cols : NS) + lane_x];
+    s.ci = a.c[tb * ns + lane_x];
+    s.ri = a.r[tb * (a.r_cols ? a.r_cols : ns) + lane_x];
     const int tF = t < T - 1 ? t : (T > 1 ? T - 2 : 0);  // there is no F_{T-1}
-    const float *Fp = a.F + ((size_t)tF * B + b) * NX * NS + lane_x;  // column lane_x of F_t[:, :NX]
-#pragma unroll
-    for (int k = 0; k < NX; ++k) s.Fcol[k] = Fp[k * NS];
+    const float *Fp = (PAD && T <= 1 ? a.C : a.F) + ((size_t)tF * B + b) * nx * ns + lane_x;  // column lane_x of F_t[:, :nx]
+    static_for<0, NX>([&](auto k) { s.Fcol[k.value] = Fp[(!PAD || k.value < nx ? k.value : 0) * ns]; });
   };
   auto step = [&](int t, const Slot &s_in) __attribute__((always_inline)) {
     const size_t tb = (size_t)t * B + b;
@@ -127,7 +114,7 @@ __global__ __launch_bounds__(256) void costate_kernel(const CostateArgs a) {
         if constexpr (PAD) { if (live && is_x) store_row(a.dF + (tb * nx + lane) * ns, row); }
         else if (live && is_x) store_contig<NS>(a.dF + (tb * NX + lane) * NS, row);
       }
-      if (a.df != nullptr && a.df_shift == 1 && live && is_x) a.df[tb * nx + lane] = a.out_sign * dlam;
+      costate_store_before(a, t, tb, nx, lane, live && is_x, lam, dlam);
     }
     // ---- dC_t, dc_t                                                          :128-129
     if (a.dC != nullptr) {
@@ -144,9 +131,7 @@ __global__ __launch_bounds__(256) void costate_kernel(const CostateArgs a) {
     if (t < T - 1) Blk::dots2_nx(nl, ndl, s.Fcol, lam, dlam);
     lam = (!PAD || is_x) ? nl : 0.f;
     dlam = (!PAD || is_x) ? ndl : 0.f;
-    if (a.df != nullptr && a.df_shift == 0 && t < T - 1 && live && is_x) a.df[tb * nx + lane] = a.out_sign * dlam;
-    if (a.lam_out != nullptr && live && is_x) a.lam_out[tb * nx + lane] = lam;
-    if (a.dlam_out != nullptr && live && is_x) a.dlam_out[tb * nx + lane] = dlam;
+    costate_store_after(a, t, tb, nx, lane, live && is_x, lam, dlam);
   };
 
   Slot sa, sb, sc;  // two steps of loads in flight
@@ -171,6 +156,7 @@ __global__ __launch_bounds__(256) void costate_kernel(const CostateArgs a) {
 struct CostateDims {
   int nx, nu;
 };
+inline size_t costate_generic_lds_bytes(int nx, int nu) { return (size_t)(2 * (nx + nu) + 4 * nx) * sizeof(float); }
 
 __global__ __launch_bounds__(64) void costate_generic_kernel(const CostateArgs a, const CostateDims d) {
   const int nx = d.nx, nu = d.nu, ns = nx + nu;
@@ -180,7 +166,7 @@ __global__ __launch_bounds__(64) void costate_generic_kernel(const CostateArgs a
   const size_t B = (size_t)a.B;
   extern __shared__ float lds[];
   float *tau = lds, *dtau = tau + ns, *lam = dtau + ns, *dlam = lam + nx, *nlam = dlam + nx, *ndlam = nlam + nx;
-  const float wa = 0.5f, wb = a.dC_mode == 0 ? 1.0f : 0.5f;
+  const float wa = kCostateWa, wb = costate_wb(a.dC_mode);
   for (int i = lane; i < nx; i += 64) { lam[i] = 0.f; dlam[i] = 0.f; }
   __syncthreads();
   for (int t = T - 1; t >= 0; --t) {
@@ -196,8 +182,7 @@ __global__ __launch_bounds__(64) void costate_generic_kernel(const CostateArgs a
           const int k = e / ns, j = e % ns;
           a.dF[tb * nx * ns + e] = a.out_sign * fmaf(dlam[k], tau[j], lam[k] * dtau[j]);
         }
-      if (a.df != nullptr && a.df_shift == 1)
-        for (int i = lane; i < nx; i += 64) a.df[tb * nx + i] = a.out_sign * dlam[i];
+      for (int i = lane; i < nx; i += 64) costate_store_before(a, t, tb, nx, i, true, lam[i], dlam[i]);
     }
     if (a.dC != nullptr)
       for (int e = lane; e < ns * ns; e += 64) {
@@ -227,9 +212,7 @@ __global__ __launch_bounds__(64) void costate_generic_kernel(const CostateArgs a
     for (int i = lane; i < nx; i += 64) {
       lam[i] = nlam[i];
       dlam[i] = ndlam[i];
-      if (a.df != nullptr && a.df_shift == 0 && t < T - 1) a.df[tb * nx + i] = a.out_sign * dlam[i];
-      if (a.lam_out != nullptr) a.lam_out[tb * nx + i] = lam[i];
-      if (a.dlam_out != nullptr) a.dlam_out[tb * nx + i] = dlam[i];
+      costate_store_after(a, t, tb, nx, i, true, lam[i], dlam[i]);
     }
     __syncthreads();
   }

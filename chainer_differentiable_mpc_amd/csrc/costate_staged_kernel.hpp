@@ -12,8 +12,7 @@
 // Before, the shapes with 17 to 32 states ran padded inside costate_kernel<32, 8, 64, PAD>: every lane fetched its row of C
 // element by element from HBM and stored its row of dC / dF the same way - 1.39 ms per sweep at (20,6), B = 4096, T = 50.
 #pragma once
-#include "costate_args.hpp"
-#include "dma_gather.hpp"   // dma_run_floats, wait_vmcnt_at_most
+#include "costate_common.hpp"   // (dma_gather.hpp: dma_run_floats, wait_vmcnt_at_most)
 
 namespace dmpc {
 
@@ -50,8 +49,8 @@ __global__ __launch_bounds__(64) void costate_staged_kernel(const CostateArgs a,
   const int rc = a.r_cols ? a.r_cols : ns;
   const CostateStagedSlot L = costate_staged_slot(nx, nu, a.r_cols);
   extern __shared__ float lds[];
-  const unsigned ring_addr = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) const char *)lds);
-  const float wa = 0.5f, wb = a.dC_mode == 0 ? 1.0f : 0.5f;
+  const unsigned ring_addr = __builtin_amdgcn_readfirstlane(lds_byte_address(lds));
+  const float wa = kCostateWa, wb = costate_wb(a.dC_mode);
   // step t is the n-th fetch, n = T - 1 - t, into slot n % depth
   auto issue = [&](int n) {
     const int slot = n % kCostateStagedDepth;
@@ -104,7 +103,7 @@ __global__ __launch_bounds__(64) void costate_staged_kernel(const CostateArgs a,
           if (j >= ns) { j -= ns; ++k; }
         }
       }
-      if (a.df != nullptr && a.df_shift == 1 && is_x) a.df[tb * nx + lane] = a.out_sign * dlam;
+      costate_store_before(a, t, tb, nx, lane, is_x, lam, dlam);
     }
     // ---- dC_t, dc_t                                                          :128-129
     if (a.dC != nullptr) {
@@ -139,9 +138,7 @@ __global__ __launch_bounds__(64) void costate_staged_kernel(const CostateArgs a,
     }
     lam = is_x ? nl : 0.f;
     dlam = is_x ? ndl : 0.f;
-    if (a.df != nullptr && a.df_shift == 0 && t < T - 1 && is_x) a.df[tb * nx + lane] = a.out_sign * dlam;
-    if (a.lam_out != nullptr && is_x) a.lam_out[tb * nx + lane] = lam;      // (left out of the counted wait, as dc / df are)
-    if (a.dlam_out != nullptr && is_x) a.dlam_out[tb * nx + lane] = dlam;
+    costate_store_after(a, t, tb, nx, lane, is_x, lam, dlam);   // (left out of the counted wait, as dc / df are)
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the fetches past t = 0 have landed before the LDS goes back)
   if (a.dx0 != nullptr && is_x) a.dx0[(size_t)b * nx + lane] = a.out_sign * dlam;

@@ -23,22 +23,15 @@ namespace dmpc {
 // come into container-sized regions of the slot as they are (all of C: its state rows are whole chunks only by chance), the
 // reads place element i of tau at lane i (state) or NX + m (control), everything outside the problem is 0, and the output
 // rows are staged at the problem's own strides.  Needs B % 4 == 0.
+// The ring layout (CostateRingLayout): the state rows of C (PAD: all rows); one staging buffer, dF rows, then dC rows.
 template <int NX, int NU, int DB, bool PAD = false>
-struct CostateWideLayout {
-  static constexpr int NS = NX + NU;
-  // 16-byte chunks of one wave-step (four trajectories): [C state rows (PAD: all rows) | c | r | F | x | u | dx | du]
-  static constexpr int nC = (PAD ? NS : NX) * NS, nc = NS, nF = NX * NS;
-  static constexpr int CH_C = 0, CH_c = CH_C + nC, CH_r = CH_c + nc, CH_F = CH_r + nc, CH_x = CH_F + nF;
-  static constexpr int CH_u = CH_x + NX, CH_dx = CH_u + NU, CH_du = CH_dx + NX, CH_END = CH_du + NU;
-  static constexpr int OFF_C = CH_C * 4, OFF_c = CH_c * 4, OFF_r = CH_r * 4, OFF_F = CH_F * 4, OFF_x = CH_x * 4;
-  static constexpr int OFF_u = CH_u * 4, OFF_dx = CH_dx * 4, OFF_du = CH_du * 4;   // in floats
-  static constexpr int kDma = (CH_END + 63) / 64;
-  static constexpr int SLOT = kDma * 256;           // floats per wave and timestep (whole 1 KB pieces)
-  static constexpr int SCR = 4 * NS * NS;           // output staging, floats per wave: dF rows, then dC rows (one buffer)
+struct CostateWideLayout : CostateRingLayout<NX, NU, DB, PAD ? NX + NU : NX, 4 * (NX + NU) * (NX + NU)> {
   // per workgroup of `waves` wavefronts (+ a zero per wave for the PAD reads).  The padded (16,8) instance does not fit a CU's
   // LDS with four wavefronts per workgroup (173 KB): it runs with three - the kernel is bound by memory, not by SIMDs
-  static constexpr size_t lds_bytes(int waves = 4) { return (size_t)waves * (DB * SLOT + SCR) * 4 + 64; }
-  static_assert((NX * NS) % 4 == 0, "a trajectory's state rows of C are whole 16-byte chunks");
+  static constexpr size_t lds_bytes(int waves = 4) {
+    return (size_t)waves * (DB * CostateWideLayout::SLOT + CostateWideLayout::SCR) * 4 + 64;
+  }
+  static_assert((NX * (NX + NU)) % 4 == 0, "a trajectory's state rows of C are whole 16-byte chunks");
 };
 
 template <int NX, int NU, int DB, bool PAD = false, int WPB = 4>
@@ -47,7 +40,6 @@ __global__ __launch_bounds__(64 * WPB) void costate_wide_kernel(const CostateArg
   using G = Group<16>;
   constexpr int NS = NX + NU, N1 = NS - 16;      // elements of tau in the second register
   static_assert(NX <= 16 && NS > 16 && NS <= 31, "tau in two registers, the state rows in the first");
-  static_assert((DB - 1) * Lay::kDma <= 63, "ring too deep for vmcnt");
 
   const int T = a.T;
   const size_t B = (size_t)a.B;
@@ -76,7 +68,7 @@ __global__ __launch_bounds__(64 * WPB) void costate_wide_kernel(const CostateArg
   const bool is_x = lane < nx;
   const bool is_t1 = lane < N1;              // this lane holds an element of tau in its second register
   const int lane_x = is_x ? lane : nx - 1;   // clamped: rows / columns re-read by the idle lanes, never used
-  const float wa = 0.5f, wb = a.dC_mode == 0 ? 1.0f : 0.5f;
+  const float wa = kCostateWa, wb = costate_wb(a.dC_mode);
 
   // per-lane source pointers of the gather groups (costate_dma_kernel.hpp; 32-bit time strides: the launcher checks them)
   unsigned long long ptr[Lay::kDma];
@@ -210,7 +202,7 @@ __global__ __launch_bounds__(64 * WPB) void costate_wide_kernel(const CostateArg
         if constexpr (PAD) store_run(a.dF + ((size_t)t * B + b0) * (nx * ns), nx * ns);
         else store_chunks<NX * NS>(scr, a.dF + ((size_t)t * B + b0) * (NX * NS), lane64);
       }
-      if (a.df != nullptr && a.df_shift == 1 && is_x) a.df[tb * nx + lane] = a.out_sign * dlam;
+      costate_store_before(a, t, tb, nx, lane, is_x, lam, dlam);
     }
     if (a.dC != nullptr) {                                                    // :128-129: rows `lane` and 16 + lane
       float row[NS];
@@ -252,9 +244,7 @@ __global__ __launch_bounds__(64 * WPB) void costate_wide_kernel(const CostateArg
     }
     lam = nl + nl2;
     dlam = ndl + ndl2;
-    if (a.df != nullptr && a.df_shift == 0 && t < T - 1 && is_x) a.df[tb * nx + lane] = a.out_sign * dlam;
-    if (a.lam_out != nullptr && is_x) a.lam_out[tb * nx + lane] = lam;
-    if (a.dlam_out != nullptr && is_x) a.dlam_out[tb * nx + lane] = dlam;
+    costate_store_after(a, t, tb, nx, lane, is_x, lam, dlam);
   };
 
   // ONE register set (lqr_wide_kernel.hpp): the slot of step t is waited for and read, then - once the reads are in -

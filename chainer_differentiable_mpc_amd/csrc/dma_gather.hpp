@@ -5,6 +5,10 @@
 
 namespace dmpc {
 
+__device__ __forceinline__ unsigned lds_byte_address(const void *p) {
+  return (unsigned)(size_t)(__attribute__((address_space(3))) const char *)p;
+}
+
 // One LDS-DMA instruction of the per-lane gather form: lane l copies the 16 bytes at its own global address to LDS at
 // M0 + OFFSET + 16 l.  The instruction offset moves the global address as well, so the pointers carry -OFFSET.
 // DMPC_DMA_NT (build flag, timing experiments): the nt cache policy on these loads.

@@ -2,7 +2,7 @@
 // Replaces DiffLqr.backward, lqr/differentiable_lqr.py:78-142:
 //   (1) d_tau  <- LqrRecursion(0, C, [grad_x;grad_u], F, 0).solve_recursion()        (:106-114)
 //   (2) lambda, d_lambda backward sweeps + outer products                             (:85-104, :115-134)
-// Step (1) is the fused solve kernel of lqr_api.hip, step (2) is costate_kernel.
+// Step (1) is the fused solve kernel of lqr_api.hip, step (2) is one of the co-state kernels (costate_path picks it).
 #include <hip/hip_runtime.h>
 
 #include "../../include/dmpc.h"
@@ -30,146 +30,131 @@ __global__ __launch_bounds__(256) void concat_tau_kernel(size_t n_rows, int nx, 
     x0[e] = 0.f;
 }
 
+// The instances: exact (nx, nu, lanes per trajectory), wide, wide containers (with wavefronts per workgroup), containers.
 #ifdef DMPC_EXPERIMENT_ONLY_8_2
 #define DMPC_COSTATE_SHAPES(X) X(8, 2, 16)
+#define DMPC_COSTATE_WIDE_SHAPES(X)
+#define DMPC_COSTATE_WIDE_CONTAINERS(X)
+#define DMPC_COSTATE_CONTAINERS(X)
+#define DMPC_COSTATE_WAVE_CONTAINERS(X)
 #else
 #define DMPC_COSTATE_SHAPES(X) \
   X(1, 1, 16) X(2, 1, 16) X(3, 1, 16) X(2, 2, 16) X(3, 2, 16) X(4, 2, 16) X(6, 2, 16) X(8, 2, 16) \
   X(4, 4, 16) X(8, 4, 16) X(12, 3, 16) X(32, 8, 64)
-#endif
-
-#ifdef DMPC_EXPERIMENT_ONLY_8_2
-#define DMPC_COSTATE_CONTAINERS(X)
-#define DMPC_COSTATE_WAVE_CONTAINERS(X)
-#define DMPC_COSTATE_WIDE_SHAPES(X)
-#define DMPC_COSTATE_WIDE_CONTAINERS(X)
-#else
-#define DMPC_COSTATE_WAVE_CONTAINERS(X) X(16, 8) X(32, 8)
 #define DMPC_COSTATE_WIDE_SHAPES(X) X(16, 4) X(16, 8) X(12, 8)   /* (12,4): 16 elements of tau - the 16-lane kernels' size, no instance yet */
-#define DMPC_COSTATE_WIDE_CONTAINERS(X) X(16, 4) X(12, 8)
+/* (16,8): 13+ states with 5+ controls; the padded instance does not fit a CU's LDS with four wavefronts per workgroup */
+#define DMPC_COSTATE_WIDE_CONTAINERS(X) X(16, 4, 4) X(12, 8, 4) X(16, 8, 3)
 #define DMPC_COSTATE_CONTAINERS(X) X(3, 1) X(4, 4) X(8, 2) X(5, 5) X(8, 4) X(14, 1) X(13, 2) X(12, 3) X(11, 4) X(10, 5) X(9, 6) X(8, 7) X(7, 8)
+#define DMPC_COSTATE_WAVE_CONTAINERS(X) X(16, 8) X(32, 8)
 #endif
 
 constexpr int kCostateDmaDepth = 4;
 
-bool costate_sums_available(int T, int B, int nx, int nu) {
-  if (B < 4 || B % 4 != 0 || T < 2 || knob_on<Knob::DMPC_NO_COSTATE_DMA>()) return false;
-#define X(NX_, NU_, L_) \
-  if (nx == NX_ && nu == NU_) return L_ == 16;
-  DMPC_COSTATE_SHAPES(X)
-#undef X
-  return false;
+// One launcher per kernel template (a.nx_log, a.nu_log: the problem's own dimensions).
+using CostateLauncher = int (*)(const CostateArgs &a, hipStream_t stream);
+template <int NX, int NU>
+static int launch_costate_dma(const CostateArgs &a, hipStream_t stream) {
+  if constexpr (NX + NU <= 16) {   // (the 16-lane shapes)
+    using Lay = CostateDmaLayout<NX, NU, kCostateDmaDepth>;
+    const int waves = (a.B + 3) / 4;
+    DMPC_LAUNCH_GGL((costate_dma_kernel<NX, NU, kCostateDmaDepth>), dim3((waves + 3) / 4), dim3(256), Lay::lds_bytes(), stream,
+                    a);
+  }
+  return (int)hipGetLastError();
+}
+template <int NX, int NU, int L, bool PAD>
+static int launch_costate_group(const CostateArgs &a, hipStream_t stream) {
+  constexpr int GPB = 256 / L;
+  DMPC_LAUNCH_GGL((costate_kernel<NX, NU, L, PAD>), dim3((a.B + GPB - 1) / GPB), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+template <int NX, int NU, bool PAD, int WPB>
+static int launch_costate_wide(const CostateArgs &a, hipStream_t stream) {
+  using Lay = CostateWideLayout<NX, NU, 2, PAD>;
+  static_assert(Lay::lds_bytes(WPB) <= 160 * 1024, "ring and staging beyond a CU's LDS");
+  if (Lay::lds_bytes(WPB) > 64 * 1024)
+    set_max_lds(reinterpret_cast<const void *>(&costate_wide_kernel<NX, NU, 2, PAD, WPB>), (int)Lay::lds_bytes(WPB));
+  DMPC_LAUNCH_GGL((costate_wide_kernel<NX, NU, 2, PAD, WPB>), dim3((a.B + 4 * WPB - 1) / (4 * WPB)), dim3(64 * WPB),
+                  Lay::lds_bytes(WPB), stream, a);
+  return (int)hipGetLastError();
+}
+static int launch_costate_staged(const CostateArgs &a, hipStream_t stream) {
+  const size_t shmem = costate_staged_lds_bytes(a.nx_log, a.nu_log, a.r_cols);
+  if (shmem > 64 * 1024) set_max_lds(reinterpret_cast<const void *>(&costate_staged_kernel), (int)shmem);
+  DMPC_LAUNCH_GGL(costate_staged_kernel, dim3(a.B), dim3(64), shmem, stream, a, a.nx_log, a.nu_log);
+  return (int)hipGetLastError();
+}
+static int launch_costate_generic(const CostateArgs &a, hipStream_t stream) {
+  DMPC_LAUNCH_GGL(costate_generic_kernel, dim3(a.B), dim3(64), costate_generic_lds_bytes(a.nx_log, a.nu_log), stream, a,
+                  CostateDims{a.nx_log, a.nu_log});
+  return (int)hipGetLastError();
 }
 
-int launch_costate(int nx, int nu, const CostateArgs &a, hipStream_t stream) {
-  if (a.dC_sum != nullptr && !costate_sums_available(a.T, a.B, nx, nu)) return DMPC_E_UNSUPPORTED;
-  // the LDS-DMA kernels move 16-byte chunks and store their rows as float4: every array they touch that way must be aligned
-  // (the entry points check C, c, F, dC, dF; the rest are the caller's tensors - a misaligned view takes the other kernels)
-  const bool al = aligned16(a.C) && aligned16(a.c) && aligned16(a.r) && aligned16(a.F) && aligned16(a.x) && aligned16(a.u) &&
-                  aligned16(a.dx) && aligned16(a.du) && aligned16(a.dC) && aligned16(a.dF);
-#define X(NX_, NU_, L_)                                                                                     \
-  if (nx == NX_ && nu == NU_) {                                                                             \
-    constexpr int GPB = 256 / L_;                                                                           \
-    if constexpr (L_ == 16) { /* inputs staged through an LDS-DMA ring (costate_dma_kernel.hpp) */          \
-      if (al && a.B >= 4 && a.B % 4 == 0 && a.T >= 2 && !knob_on<Knob::DMPC_NO_COSTATE_DMA>()) {                             \
-        using Lay = CostateDmaLayout<NX_, NU_, kCostateDmaDepth>;                                           \
-        const int waves = (a.B + 3) / 4;                                                                    \
-        DMPC_LAUNCH_GGL((costate_dma_kernel<NX_, NU_, kCostateDmaDepth>), dim3((waves + 3) / 4), dim3(256), \
-                           Lay::lds_bytes(), stream, a);                                                    \
-        return (int)hipGetLastError();                                                                      \
-      }                                                                                                     \
-    }                                                                                                       \
-    DMPC_LAUNCH_GGL((costate_kernel<NX_, NU_, L_>), dim3((a.B + GPB - 1) / GPB), dim3(256), 0, stream, a); \
-    return (int)hipGetLastError();                                                                          \
-  }
+// Which kernel takes a sweep: its launcher, or nullptr where none does.  Every kernel is one row here; nothing is launched.
+// forms_sums: the kernel forms dC_sum / dc_sum - the 16-lane LDS-DMA kernel alone does, the others would leave them untouched,
+// so a sweep that wants the sums (wants_sums) and would take one of those is unsupported.
+static CostateLauncher costate_path(int T, int B, int nx, int nu, bool aligned, bool wants_sums) {
+  const int ns = nx + nu;
+  auto take = [&](CostateLauncher launch, bool forms_sums = false) { return wants_sums && !forms_sums ? nullptr : launch; };
+  // The LDS-DMA ring kernels give a wavefront four trajectories (whole wavefronts only), fetch two steps before they compute,
+  // move 16-byte chunks and store their rows as float4: every array they touch that way must be aligned (the entry points
+  // check C, c, F, dC, dF; the rest are the caller's tensors - a misaligned view takes the other kernels)
+  const bool ring = aligned && B >= 4 && B % 4 == 0 && T >= 2 && !knob_on<Knob::DMPC_NO_COSTATE_DMA>();
+#define X(NX_, NU_, L_)       \
+  if (nx == NX_ && nu == NU_) \
+    return L_ == 16 && ring ? take(launch_costate_dma<NX_, NU_>, true) : take(launch_costate_group<NX_, NU_, L_, false>);
   DMPC_COSTATE_SHAPES(X)
 #undef X
   // 17 to 31 elements of tau, at most 16 states: four trajectories per wavefront with tau in two registers
-  // (costate_wide_kernel.hpp; before, a wavefront per trajectory inside the (16,8) container).  DMPC_NO_WIDE=1: that path.
-  {
-    if (!knob_on<Knob::DMPC_NO_WIDE>() && al && a.dC_sum == nullptr && a.B >= 4 && a.B % 4 == 0 && a.T >= 2 &&
-        !knob_on<Knob::DMPC_NO_COSTATE_DMA>() &&
-        (size_t)a.B * (nx + nu) * (nx + nu) * 4 < ((size_t)1 << 31)) {
-#define X(NX_, NU_)                                                                                            \
-  if (nx == NX_ && nu == NU_) {                                                                                \
-    using Lay = CostateWideLayout<NX_, NU_, 2>;                                                                \
-    static_assert(Lay::lds_bytes() <= 160 * 1024, "ring and staging beyond a CU's LDS");                      \
-    if (Lay::lds_bytes() > 64 * 1024)                                                                          \
-      set_max_lds(reinterpret_cast<const void *>(&costate_wide_kernel<NX_, NU_, 2>), \
-                                (int)Lay::lds_bytes());           \
-    DMPC_LAUNCH_GGL((costate_wide_kernel<NX_, NU_, 2>), dim3((a.B + 15) / 16), dim3(256), Lay::lds_bytes(), stream, a); \
-    return (int)hipGetLastError();                                                                             \
-  }
-      DMPC_COSTATE_WIDE_SHAPES(X)
+  // (costate_wide_kernel.hpp, 32-bit time strides; before, a wavefront per trajectory inside the (16,8) container).
+  // DMPC_NO_WIDE=1: that path.
+  const bool wide = ring && !knob_on<Knob::DMPC_NO_WIDE>() && (size_t)B * ns * ns * 4 < ((size_t)1 << 31);
+#define X(NX_, NU_) \
+  if (wide && nx == NX_ && nu == NU_) return take(launch_costate_wide<NX_, NU_, false, 4>);
+  DMPC_COSTATE_WIDE_SHAPES(X)
 #undef X
-      // ... and padded inside the (16,4), (12,8) or (16,8) instance: the shapes without a 16-lane container (nx + nu >= 16), and
-      // the larger ones of those with one - the 16-lane container stores its rows of dC / dF element by element, this kernel
-      // stages them: gradient at B = 4096, T = 50 (9,4) 400 -> 295 us, (11,4) 530 -> 309, (13,2) 568 -> 321; below 13
-      // elements of tau the container wins ((6,3) 208 against 247 us).  DMPC_COSTATE_WIDE_MIN_NS moves the threshold.
-      if (!knob_on<Knob::DMPC_NO_CONTAINER>() && nx + nu >= knob_int<Knob::DMPC_COSTATE_WIDE_MIN_NS>() && nx >= 1 && nu >= 1) {
-        CostateArgs p = a;
-        p.nx_log = nx;
-        p.nu_log = nu;
-#define X(NX_, NU_)                                                                                            \
-  if (nx <= NX_ && nu <= NU_) {                                                                                \
-    using Lay = CostateWideLayout<NX_, NU_, 2, true>;                                                          \
-    static_assert(Lay::lds_bytes() <= 160 * 1024, "ring and staging beyond a CU's LDS");                      \
-    if (Lay::lds_bytes() > 64 * 1024)                                                                          \
-      set_max_lds(reinterpret_cast<const void *>(&costate_wide_kernel<NX_, NU_, 2, true>), \
-                                (int)Lay::lds_bytes());           \
-    DMPC_LAUNCH_GGL((costate_wide_kernel<NX_, NU_, 2, true>), dim3((p.B + 15) / 16), dim3(256), Lay::lds_bytes(), stream, p); \
-    return (int)hipGetLastError();                                                                             \
-  }
-        DMPC_COSTATE_WIDE_CONTAINERS(X)
+  // ... and padded inside the (16,4), (12,8) or (16,8) instance: the shapes without a 16-lane container (nx + nu >= 16), and
+  // the larger ones of those with one - the 16-lane container stores its rows of dC / dF element by element, this kernel
+  // stages them: gradient at B = 4096, T = 50 (9,4) 400 -> 295 us, (11,4) 530 -> 309, (13,2) 568 -> 321; below 13
+  // elements of tau the container wins ((6,3) 208 against 247 us).  DMPC_COSTATE_WIDE_MIN_NS moves the threshold.
+  const bool container = !knob_on<Knob::DMPC_NO_CONTAINER>();
+  const bool wide_padded = wide && container && ns >= knob_int<Knob::DMPC_COSTATE_WIDE_MIN_NS>() && nx >= 1 && nu >= 1;
+#define X(NX_, NU_, WPB_) \
+  if (wide_padded && nx <= NX_ && nu <= NU_) return take(launch_costate_wide<NX_, NU_, true, WPB_>);
+  DMPC_COSTATE_WIDE_CONTAINERS(X)
 #undef X
-        if (nx <= 16 && nu <= 8) {   // 13+ states with 5+ controls: the (16,8) instance, three wavefronts per workgroup (LDS)
-          using Lay = CostateWideLayout<16, 8, 2, true>;
-          constexpr int kWaves = 3;
-          static_assert(Lay::lds_bytes(kWaves) <= 160 * 1024, "ring and staging beyond a CU's LDS");
-          set_max_lds(reinterpret_cast<const void *>(&costate_wide_kernel<16, 8, 2, true, kWaves>), (int)Lay::lds_bytes(kWaves));
-          DMPC_LAUNCH_GGL((costate_wide_kernel<16, 8, 2, true, kWaves>), dim3((p.B + 4 * kWaves - 1) / (4 * kWaves)),
-                          dim3(64 * kWaves), Lay::lds_bytes(kWaves), stream, p);
-          return (int)hipGetLastError();
-        }
-      }
-    }
-  }
-  {   // a problem without a specialisation padded inside the first container that holds it (the lists of lqr_api.hip)
-    if (!knob_on<Knob::DMPC_NO_CONTAINER>() && a.dC_sum == nullptr) {
-      CostateArgs p = a;
-      p.nx_log = nx;
-      p.nu_log = nu;
-#define X(NX_, NU_)                                                                                          \
-  if (nx <= NX_ && nu <= NU_) {                                                                              \
-    DMPC_LAUNCH_GGL((costate_kernel<NX_, NU_, 16, true>), dim3((p.B + 15) / 16), dim3(256), 0, stream, p);  \
-    return (int)hipGetLastError();                                                                           \
-  }
-      DMPC_COSTATE_CONTAINERS(X)
+  // a problem without a specialisation padded inside the first container that holds it (the lists of lqr_api.hip)
+#define X(NX_, NU_) \
+  if (container && nx <= NX_ && nu <= NU_) return take(launch_costate_group<NX_, NU_, 16, true>);
+  DMPC_COSTATE_CONTAINERS(X)
 #undef X
-      {   // wider (17+ states, ragged batches of the wide shapes): a wavefront per trajectory, the step's blocks through an
-          // LDS ring at the problem's own dimensions (costate_staged_kernel.hpp); DMPC_NO_STAGED_COSTATE=1: the containers below
-        const size_t shmem = costate_staged_lds_bytes(nx, nu, a.r_cols);
-        if (!knob_on<Knob::DMPC_NO_STAGED_COSTATE>() && a.T >= 2 && nx + nu <= 63 && shmem <= 150 * 1024) {
-          if (shmem > 64 * 1024)
-            set_max_lds(reinterpret_cast<const void *>(&costate_staged_kernel), (int)shmem);
-          DMPC_LAUNCH_GGL(costate_staged_kernel, dim3(a.B), dim3(64), shmem, stream, a, nx, nu);
-          return (int)hipGetLastError();
-        }
-      }
-#define X(NX_, NU_)                                                                                          \
-  if (nx <= NX_ && nu <= NU_) {   /* wider: a wavefront per trajectory */                                     \
-    DMPC_LAUNCH_GGL((costate_kernel<NX_, NU_, 64, true>), dim3((p.B + 3) / 4), dim3(256), 0, stream, p);     \
-    return (int)hipGetLastError();                                                                           \
-  }
-      DMPC_COSTATE_WAVE_CONTAINERS(X)
+  // wider (17+ states, ragged batches of the wide shapes): a wavefront per trajectory, the step's blocks through an LDS ring
+  // at the problem's own dimensions (costate_staged_kernel.hpp; r_cols = 0: the longest rows of r).
+  // DMPC_NO_STAGED_COSTATE=1: the containers below
+  if (container && !knob_on<Knob::DMPC_NO_STAGED_COSTATE>() && T >= 2 && ns <= 63 &&
+      costate_staged_lds_bytes(nx, nu, 0) <= 150 * 1024)
+    return take(launch_costate_staged);
+#define X(NX_, NU_) \
+  if (container && nx <= NX_ && nu <= NU_) return take(launch_costate_group<NX_, NU_, 64, true>);
+  DMPC_COSTATE_WAVE_CONTAINERS(X)
 #undef X
-    }
-  }
   // runtime dimensions, a wavefront per trajectory, vectors in LDS: any size the vectors fit (the reference has no limit)
-  const size_t shmem = (size_t)(2 * (nx + nu) + 4 * nx) * sizeof(float);
-  if (shmem > 64 * 1024) return DMPC_E_UNSUPPORTED;
-  DMPC_LAUNCH_GGL(costate_generic_kernel, dim3(a.B), dim3(64), shmem, stream, a, CostateDims{nx, nu});
-  return (int)hipGetLastError();
+  return take(costate_generic_lds_bytes(nx, nu) <= 64 * 1024 ? launch_costate_generic : nullptr);
+}
+
+bool costate_sums_available(int T, int B, int nx, int nu, bool aligned) {
+  return costate_path(T, B, nx, nu, aligned, true) != nullptr;
+}
+
+int launch_costate(int nx, int nu, const CostateArgs &args, hipStream_t stream) {
+  const bool al = aligned16(args.C) && aligned16(args.c) && aligned16(args.r) && aligned16(args.F) && aligned16(args.x) &&
+                  aligned16(args.u) && aligned16(args.dx) && aligned16(args.du) && aligned16(args.dC) && aligned16(args.dF);
+  const CostateLauncher launch = costate_path(args.T, args.B, nx, nu, al, args.dC_sum != nullptr);
+  if (launch == nullptr) return DMPC_E_UNSUPPORTED;   // (nothing launched)
+  CostateArgs a = args;
+  a.nx_log = nx;
+  a.nu_log = nu;
+  return launch(a, stream);
 }
 
 struct KktWs {

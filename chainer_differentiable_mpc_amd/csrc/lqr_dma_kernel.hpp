@@ -26,10 +26,6 @@
 
 namespace dmpc {
 
-__device__ __forceinline__ unsigned lds_byte_address(const void *p) {
-  return (unsigned)(size_t)(__attribute__((address_space(3))) const char *)p;
-}
-
 // One DMA instruction: 64 lanes x 16 bytes, global (sbase + voff) -> LDS (m0 + lane*16).  hipcc does not use M0
 // in these kernels (no LDS-DMA builtin, no movrel), so it is written without save/restore; the instruction
 // between the M0 write and the DMA provides the required wait state.

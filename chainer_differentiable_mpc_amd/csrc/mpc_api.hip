@@ -997,8 +997,11 @@ int dmpc_mpc_step_backward(int T, int B, int nx, int nu, const float *C_hat, con
   if (T <= 1 || B <= 0 || nx <= 0 || nu <= 0) return DMPC_E_BADARG;
   if (!C_hat || !c_hat || !F_hat || !x || !u || !u_lower || !u_upper || !d_x_init || !ws) return DMPC_E_BADARG;
   if ((dC_sum == nullptr) != (dc_sum == nullptr) || (dc == nullptr && dc_sum == nullptr)) return DMPC_E_BADARG;
-  // the sums are formed by the LDS-DMA co-state kernel only (whole wavefronts of four trajectories, 16-lane shapes)
-  if (dC_sum != nullptr && !costate_sums_available(T, B, nx, nu)) return DMPC_E_UNSUPPORTED;   // (nothing launched)
+  // the sums are formed by the LDS-DMA co-state kernel only (whole wavefronts of four trajectories, 16-lane shapes, 16-byte
+  // aligned arrays - the workspace's own are aligned by construction)
+  const bool al = aligned16(x) && aligned16(u) && aligned16(C_hat) && aligned16(c_hat) && aligned16(F_hat) && aligned16(dC) &&
+                  aligned16(dF);
+  if (dC_sum != nullptr && !costate_sums_available(T, B, nx, nu, al)) return DMPC_E_UNSUPPORTED;   // (nothing launched)
   if (!aligned16(C_hat) || !aligned16(c_hat) || !aligned16(F_hat) || !aligned16(dC) || !aligned16(dF))
     return DMPC_E_BADARG;
   const MpcWs w = mpc_layout(T, B, nx, nu);

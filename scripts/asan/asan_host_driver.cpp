@@ -111,6 +111,15 @@ int main() {
           EXPECT(dmpc_lqr_shared_kkt_grad(T, B, nx, nu, 0, p, p, p, p, p, ws, p, p, 0, p, p, p, p, p, ws, gwb - 1, pi, nullptr) ==
                  DMPC_E_WORKSPACE);
         }
+  {   // MPCstep.backward's tiled-cost sums come from the LDS-DMA co-state kernel alone, which moves x and u in 16-byte chunks:
+      // a view of x four bytes off is refused before anything is launched; the aligned call goes on to its launches (no device)
+    float *x4 = reinterpret_cast<float *>(0x1004);
+    const size_t mwb = dmpc_mpc_step_workspace_bytes(20, 4, 8, 2);
+    EXPECT(dmpc_mpc_step_backward(20, 4, 8, 2, p, p, p, x4, p, p, p, p, p, p, nullptr, nullptr, nullptr, nullptr, p, p, nullptr,
+                                  nullptr, 0.f, ws, mwb, pi, nullptr) == DMPC_E_UNSUPPORTED);
+    EXPECT(dmpc_mpc_step_backward(20, 4, 8, 2, p, p, p, p, p, p, p, p, p, p, nullptr, nullptr, nullptr, nullptr, p, p, nullptr,
+                                  nullptr, 0.f, ws, mwb, pi, nullptr) != DMPC_E_UNSUPPORTED);
+  }
   EXPECT(dmpc_lqr_shared_workspace_bytes(0, 1, 1, 1) == 0 && dmpc_lqr_shared_saved_bytes(0, 1, 1) == 0);
   EXPECT(dmpc_lqr_kernel_family(0, 3) == DMPC_E_UNSUPPORTED);
   EXPECT(dmpc_lqr_workspace_bytes(0, 1, 1, 1) == 0);

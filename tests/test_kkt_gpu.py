@@ -161,6 +161,86 @@ def test_misaligned_solution_views_give_the_aligned_result(dims):
         assert_close(npy(a), npy(b), TOLS[key], key)
 
 
+# the smallest (T, B, nx, nu) at which launch_costate (kkt_api.hip) still takes each of its kernels, and the kernel's name
+COSTATE_PATHS = [((4, 8, 3, 1), "void dmpc::costate_dma_kernel<3, 1, 4>"),             # 16 lanes, LDS-DMA ring
+                 ((4, 6, 3, 1), "void dmpc::costate_kernel<3, 1, 16, false>"),         # ragged batch: register prefetch
+                 ((5, 8, 3, 3), "void dmpc::costate_kernel<4, 4, 16, true>"),          # 16-lane container
+                 ((3, 8, 12, 8), "void dmpc::costate_wide_kernel<12, 8, 2, false, 4>"),   # wide, exact
+                 ((3, 8, 9, 4), "void dmpc::costate_wide_kernel<16, 4, 2, true, 4>"),     # wide, padded
+                 ((3, 8, 14, 6), "void dmpc::costate_wide_kernel<16, 8, 2, true, 3>"),    # wide, padded, three wavefronts
+                 ((3, 5, 14, 6), "dmpc::costate_staged_kernel"),                          # ragged batch of a wide shape
+                 ((3, 3, 20, 6), "dmpc::costate_staged_kernel"),                          # 17+ states
+                 ((3, 4, 32, 8), "void dmpc::costate_kernel<32, 8, 64, false>"),       # a wavefront per trajectory
+                 ((3, 4, 40, 30), "dmpc::costate_generic_kernel")]                        # more than 63 elements of tau
+
+
+@pytest.mark.parametrize("case,kernel", COSTATE_PATHS, ids=["T%d_B%d_%dx%d" % c for c, _ in COSTATE_PATHS])
+def test_costate_sweep_takes_its_kernel_and_matches_the_oracle(case, kernel):
+    """one case per kernel the co-state sweep can take: the kernel by name (the gradient without saved gains ends with the
+    sweep's launch), and the gradient against the oracle"""
+    from chainer_differentiable_mpc_amd import _lib
+    T, B, nx, nu = case
+    p = synthetic.make_lqr_problem(B, T, nx, nu, seed=700 + 3 * nx + B)
+    rng = np.random.RandomState(nx * 23 + nu + B)
+    gx = rng.randn(T, B, nx).astype(np.float32).astype(np.float64)
+    gu = rng.randn(T, B, nu).astype(np.float32).astype(np.float64)
+    xr, ur = olqr.lqr_solve(p["x_init"], p["C"], p["c"], p["F"], p["f"], T, nx, nu)
+    ref = okkt.difflqr_backward(p["x_init"], p["C"], p["c"], p["F"], xr, ur, gx, gu, T, nx, nu)
+    d = to_dev(p)
+    x, u = solve_device(d["C"], d["c"], d["F"], d["f"], d["x_init"], None, T, nx, nu)[:2]
+    got = kkt_grad_device(d["C"], d["c"], d["F"], x, u, torch.as_tensor(gx, dtype=torch.float32).cuda(),
+                          torch.as_tensor(gu, dtype=torch.float32).cuda(), T, nx, nu)
+    torch.cuda.synchronize()
+    name = _lib.last_kernel_name()
+    print(case, name)
+    assert name.startswith(kernel), name
+    for a, want, key in zip(got, ref, KEYS):
+        assert_close(npy(a), want, TOLS[key], key)
+
+
+def test_tiled_cost_sums_are_refused_for_a_misaligned_solution_view():
+    """dC_sum / dc_sum come from the LDS-DMA co-state kernel alone, which moves x and u in 16-byte chunks: with x a contiguous
+    view four bytes off the entry point declines before it launches anything (`tiled_cost_gradient` -> None, the caller
+    reduces the dense gradient); with the aligned tensor the sums are the dense gradient's, reduced."""
+    from chainer_differentiable_mpc_amd import _lib
+    from chainer_differentiable_mpc_amd.lqr_recursion import _workspace
+    from chainer_differentiable_mpc_amd.mpc_step import tiled_cost_gradient
+    T, B, nx, nu = 3, 4, 3, 1
+    ns = nx + nu
+    dev = torch.device("cuda", 0)
+    p = synthetic.make_lqr_problem(B, T, nx, nu, seed=910, with_f=False)
+    g = torch.Generator(device="cpu").manual_seed(911)
+    r = dict(C=to_dev(p)["C"], c=to_dev(p)["c"], F=to_dev(p)["F"], x=torch.randn(T, B, nx, generator=g).cuda(),
+             u=(0.5 * torch.rand(T, B, nu, generator=g) - 0.25).cuda())
+    lo, hi = torch.full((T, B, nu), -0.2, device="cuda"), torch.full((T, B, nu), 0.2, device="cuda")   # some controls beyond it
+    gx, gu = torch.randn(T, B, nx, generator=g).cuda(), torch.randn(T, B, nu, generator=g).cuda()
+
+    def off(t):
+        buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
+        v = buf[1:].view(t.shape)
+        v.copy_(t)
+        assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+        return v
+    assert tiled_cost_gradient(T, B, nx, nu, dev, dict(r, x=off(r["x"])), lo, hi, gx, gu) is None
+    got = tiled_cost_gradient(T, B, nx, nu, dev, r, lo, hi, gx, gu)
+    assert got is not None
+    # the dense call: dC [T,B,ns,ns], dc [T,B,ns]
+    lib = _lib.load()
+    dx0, dC, dc = torch.empty(B, nx, device=dev), torch.empty(T, B, ns, ns, device=dev), torch.empty(T, B, ns, device=dev)
+    need = lib.dmpc_mpc_step_workspace_bytes(T, B, nx, nu)
+    ws = _workspace(need, dev)
+    with _lib.guard(dev):
+        rc = lib.dmpc_mpc_step_backward(T, B, nx, nu, _lib.ptr(r["C"]), _lib.ptr(r["c"]), _lib.ptr(r["F"]), _lib.ptr(r["x"]),
+                                        _lib.ptr(r["u"]), _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(gx), _lib.ptr(gu), _lib.ptr(dx0),
+                                        _lib.ptr(dC), _lib.ptr(dc), None, None, None, None, None, None, 0.0, _lib.ptr(ws), need,
+                                        None, _lib.stream_ptr(dev))
+    _lib.check(rc, "dmpc_mpc_step_backward")
+    assert np.abs(npy(dC)).max() > 1e-3
+    assert_close(npy(got[1]), npy(dC).sum((0, 1)), TOL_PRIMAL, "dC_sum")
+    assert_close(npy(got[2]), npy(dc).sum((0, 1)), TOL_PRIMAL, "dc_sum")
+    assert_close(npy(got[0]), npy(dx0), TOL_COSTATE, "dx_init")
+
+
 def test_autograd_through_lqrnet_reproduces_the_notebook_anchor():
     """examples/LQRnet.ipynb:184 - loss 0.661925 at iteration 0, dynamics mse 4.774785 after the first
     RMSprop step - with forward AND backward on the HIP path, driven by torch.autograd."""
