@@ -62,6 +62,9 @@ SIGNATURES = {
     "dmpc_mpc_forward_rec": (_c_i, [_c_i] * 4 + [_c_f] * 10 + [ctypes.c_float, _c_i] + [_c_f] * 10),
     "dmpc_mpc_forward_rec_pendulum": (_c_i, [_c_i] * 2 + [_c_f] * 8 + [ctypes.c_float] * 6 + [_c_i] + [_c_f] * 10),
     "dmpc_pendulum_rollout_linearize": (_c_i, [_c_i] * 2 + [_c_f] * 2 + [ctypes.c_float] * 5 + [_c_i] + [_c_f] * 4),
+    "dmpc_mlp_dx_supported": (_c_i, [_c_i] * 4),
+    "dmpc_mlp_rollout_linearize": (_c_i, [_c_i] * 7 + [_c_f] * 10),
+    "dmpc_mpc_forward_rec_mlp": (_c_i, [_c_i] * 7 + [_c_f] * 12 + [ctypes.c_float, _c_i] + [_c_f] * 10),
     "dmpc_mpc_step_backward": (_c_i, [_c_i] * 4 + [_c_f] * 9 + [_c_f] * 7 + [_c_f, _c_f, ctypes.c_float]
                                + [_c_f, _c_sz, _c_f, _c_f]),
     "dmpc_lin_rollout": (_c_i, [_c_i] * 4 + [_c_f] * 6),

@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from .approximate import approximate_cost, linearize_dynamics
 from .lqr_recursion import _as_tensor, _device_of, _workspace
-from .mpc_step import MPCstep, _MPCstepTiledDxFn, _MPCstepTiledFn
+from .mpc_step import MPCstep, _MPCstepTiledDxFn, _MPCstepTiledFn, _is_simple_pendulum
 from .util import LinDx, QuadCost, TiledLinDx, TiledQuadCost, get_cost, get_traj
 
 
@@ -186,7 +186,7 @@ class BoxDDP(torch.nn.Module):
         ns = nx + nu
         if isinstance(dynamics, LinDx):
             kind, params, Fd, fd = 0, None, dynamics.F, dynamics.f
-        elif hasattr(dynamics, "fused_ok") and dynamics.fused_ok(x_init, u) and (nx, nu) == (3, 1):
+        elif _is_simple_pendulum(dynamics) and dynamics.fused_ok(x_init, u) and (nx, nu) == (3, 1):
             g_, m_, l_ = dynamics.host_params()
             params = (ctypes.c_float * 6)(g_, m_, l_, float(dynamics.dt), float(dynamics.max_torque),
                                           1.0 if dynamics.clamp_grad_closed else 0.0)

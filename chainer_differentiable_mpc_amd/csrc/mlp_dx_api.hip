@@ -1,0 +1,64 @@
+// mlp_dx_api.hip - C-ABI entry points of the learned one-hidden-layer dynamics model (include/dmpc.h section E,
+// "MlpDx"): the nominal rollout with its analytic linearisation, and MPCstep.forward_rec with the network as the true
+// dynamics.  Every argument and size check comes before the first HIP call.
+#include <hip/hip_runtime.h>
+
+#include "../../include/dmpc.h"
+#include "api_util.hpp"
+#include "mlp_dx_kernels.hpp"
+
+namespace dmpc {
+
+// 0: launch; DMPC_E_BADARG / DMPC_E_UNSUPPORTED otherwise
+static int mlp_check(int nx, int nu, int n_hidden, int act) {
+  if (nx <= 0 || nu <= 0) return DMPC_E_BADARG;
+  if (act != 0) return DMPC_E_UNSUPPORTED;
+  if (nx > kMlpMaxNx || nu > kMlpMaxNu || n_hidden < 1 || n_hidden > kMlpMaxHidden) return DMPC_E_UNSUPPORTED;
+  return 0;
+}
+
+}  // namespace dmpc
+
+using namespace dmpc;
+
+extern "C" {
+
+int dmpc_mlp_dx_supported(int nx, int nu, int n_hidden, int act) { return mlp_check(nx, nu, n_hidden, act) == 0 ? 1 : 0; }
+
+int dmpc_mlp_rollout_linearize(int T, int B, int nx, int nu, int n_hidden, int act, int residual, const float *W1,
+                               const float *b1, const float *W2, const float *b2, const float *x_init, const float *u,
+                               float *x_out, float *F_out, float *f_out, dmpc_stream_t stream_) {
+  if (T <= 0 || B <= 0 || nx <= 0 || nu <= 0) return DMPC_E_BADARG;
+  if (!W1 || !b1 || !W2 || !b2 || !x_init || !u || !x_out) return DMPC_E_BADARG;
+  if (f_out != nullptr && F_out == nullptr) return DMPC_E_BADARG;
+  const int rc = mlp_check(nx, nu, n_hidden, act);
+  if (rc != 0) return rc;
+  if ((size_t)T * B * nx * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;
+  MlpRolloutArgs ra{T, B, MlpModel{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2}, x_init, u, x_out, F_out, f_out};
+  DMPC_LAUNCH_GGL(mlp_rollout_linearize_kernel, dim3((B + kMlpWaves - 1) / kMlpWaves), dim3(64 * kMlpWaves),
+                  mlp_lds_bytes(nx, nu, n_hidden), static_cast<hipStream_t>(stream_), ra);
+  return (int)hipGetLastError();
+}
+
+int dmpc_mpc_forward_rec_mlp(int T, int B, int nx, int nu, int n_hidden, int act, int residual, const float *W1,
+                             const float *b1, const float *W2, const float *b2, const float *Ks, const float *ks,
+                             const float *controls, const float *states, const float *u_lower, const float *u_upper,
+                             const float *C_true, const float *c_true, float ls_decay, int max_ls_iter, float *x_out,
+                             float *u_out, float *costs, float *old_costs, float *alphas, float *objs, float *u_first,
+                             int32_t *n_ls_iter, int32_t *info, dmpc_stream_t stream_) {
+  if (T <= 1 || B <= 0 || nx <= 0 || nu <= 0) return DMPC_E_BADARG;
+  if (!W1 || !b1 || !W2 || !b2 || !Ks || !ks || !controls || !states || !u_lower || !u_upper || !C_true || !c_true ||
+      !x_out || !u_out || !costs || !alphas || !n_ls_iter)
+    return DMPC_E_BADARG;
+  const int rc = mlp_check(nx, nu, n_hidden, act);
+  if (rc != 0) return rc;
+  if ((size_t)T * B * (nx + nu) * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;
+  MpcFwdArgs fa{T, B, Ks, ks, controls, states, u_lower, u_upper, C_true, c_true, nullptr, nullptr, ls_decay,
+                max_ls_iter, /*ls_cap=*/64, x_out, u_out, u_first, costs, old_costs, alphas, objs, n_ls_iter, info};
+  const MlpModel m{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2};
+  DMPC_LAUNCH_GGL(mpc_forward_rec_mlp_kernel, dim3((B + kMlpWaves - 1) / kMlpWaves), dim3(64 * kMlpWaves),
+                  mlp_lds_bytes(nx, nu, n_hidden), static_cast<hipStream_t>(stream_), fa, m);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -1,0 +1,151 @@
+"""`MlpDx` - a learned one-hidden-layer dynamics model for `BoxDDP` / `MPCstep`:
+
+    next(x, u) = W2 tanh(W1 [x;u] + b1) + b2 (+ x when residual)
+
+`forward` is torch code (CPU and GPU tensors).  On the GPU, at a size the kernels serve (nx <= 16, nu <= 8, n_hidden <= 256),
+the nominal rollout with its analytic linearisation is one launch (`dmpc_mlp_rollout_linearize`) and `MPCstep`'s line search
+evaluates the network inside its kernel (`dmpc_mpc_forward_rec_mlp`); the hooks are the ones `PendulumDx` has (`linearize`,
+`fused_ok`, `rollout_linearize`).  The weights go to the library as device pointers on every call: nothing is read back and
+nothing is cached, so an optimiser step in place is seen by the next call.
+
+Learning the weights follows mpc/approximate.py:77-119: the Jacobians F_t are constants of the graph, f_t = next - F_t [x;u]
+stays on it through `next` and the re-rolled states, and `MPCstep.backward`'s df reaches W1, b1, W2, b2."""
+import math
+
+import torch
+
+from . import _lib
+from .util import bmv
+
+ACT_TANH = 0     # the `act` argument of the C ABI
+
+
+class MlpDx(torch.nn.Module):
+    def __init__(self, n_state, n_ctrl, n_hidden, residual=True, seed=None):
+        super().__init__()
+        self.n_state, self.n_ctrl, self.n_hidden = int(n_state), int(n_ctrl), int(n_hidden)
+        self.residual = bool(residual)
+        ns = self.n_state + self.n_ctrl
+        gen = None if seed is None else torch.Generator().manual_seed(int(seed))
+        self.W1 = torch.nn.Parameter(0.5 * torch.randn(self.n_hidden, ns, generator=gen) / math.sqrt(ns))
+        self.b1 = torch.nn.Parameter(torch.zeros(self.n_hidden))
+        self.W2 = torch.nn.Parameter(0.5 * torch.randn(self.n_state, self.n_hidden, generator=gen) / math.sqrt(self.n_hidden))
+        self.b2 = torch.nn.Parameter(torch.zeros(self.n_state))
+        self._size_ok = None
+
+    def _weights(self):
+        return self.W1, self.b1, self.W2, self.b2
+
+    def _hidden(self, x, u):
+        W1, b1 = self.W1.to(x), self.b1.to(x)
+        return torch.tanh(torch.cat((x, u), dim=-1) @ W1.t() + b1)
+
+    def _output(self, a, x):
+        nxt = a @ self.W2.to(x).t() + self.b2.to(x)
+        return nxt + x if self.residual else nxt
+
+    def forward(self, x, u):
+        """x [B,nx] (or [nx]), u [B,nu] (or [nu]) -> next state"""
+        assert x.shape[-1] == self.n_state and u.shape[-1] == self.n_ctrl and x.shape[:-1] == u.shape[:-1]
+        return self._output(self._hidden(x, u), x)
+
+    def _jacobian(self, a):
+        """d next / d [x;u] at the hidden activations a [B,H] -> [B,nx,ns], a constant of the graph"""
+        a = a.detach()
+        F = torch.einsum("ih,bh,hj->bij", self.W2.detach().to(a), 1.0 - a * a, self.W1.detach().to(a))
+        if self.residual:
+            F = F + torch.eye(self.n_state, self.n_state + self.n_ctrl, dtype=a.dtype, device=a.device)
+        return F
+
+    # ------------------------------------------------------------------ the device path
+    def supported(self):
+        """the kernels serve this size (asked of the library once; nothing is launched)"""
+        if self._size_ok is None:
+            self._size_ok = bool(_lib.load().dmpc_mlp_dx_supported(self.n_state, self.n_ctrl, self.n_hidden, ACT_TANH))
+        return self._size_ok
+
+    def _on_device(self, x_init, u):
+        return isinstance(x_init, torch.Tensor) and isinstance(u, torch.Tensor) and x_init.is_cuda and u.is_cuda and \
+            self.supported()
+
+    def _grad_wanted(self, *tensors):
+        return torch.is_grad_enabled() and (any(p.requires_grad for p in self._weights()) or
+                                            any(t.requires_grad for t in tensors))
+
+    def fused_ok(self, x_init, u):
+        """the one-launch rollout + linearisation applies: GPU tensors, a supported size, no gradient wanted now"""
+        return self._on_device(x_init, u) and not self._grad_wanted(x_init, u)
+
+    def device_weights(self, device):
+        """(W1, b1, W2, b2) as the kernels take them - contiguous float32 on `device`; made on every call, never kept"""
+        return tuple(_lib.f32c(p.detach(), device) for p in self._weights())
+
+    def rollout_linearize(self, x_init, u, want_model=True):
+        """(x [T,B,nx], F [T-1,B,nx,ns], f [T-1,B,nx]) from x_init [B,nx], u [T,B,nu] in one kernel launch
+        (`dmpc_mlp_rollout_linearize`): get_traj + linearize_dynamics of the reference's BoxDDP loop.  F = f = None without
+        want_model.  CPU tensors or a size outside the kernels' limits: the same results from torch."""
+        T, B = u.shape[0], u.shape[1]
+        nx, nu = self.n_state, self.n_ctrl
+        if not self._on_device(x_init, u):
+            with torch.no_grad():
+                return self._rollout_linearize_torch(x_init.detach(), u.detach(), want_model)
+        lib = _lib.load()
+        d = x_init.device
+        x0, ud = _lib.f32c(x_init.detach(), d), _lib.f32c(u.detach(), d)
+        assert list(x0.shape) == [B, nx] and list(ud.shape) == [T, B, nu]
+        W1, b1, W2, b2 = self.device_weights(d)
+        x = torch.empty((T, B, nx), dtype=torch.float32, device=d)
+        F = torch.empty((max(T - 1, 0), B, nx, nx + nu), dtype=torch.float32, device=d) if want_model else None
+        f = torch.empty((max(T - 1, 0), B, nx), dtype=torch.float32, device=d) if want_model else None
+        with _lib.guard(d):
+            rc = lib.dmpc_mlp_rollout_linearize(T, B, nx, nu, self.n_hidden, ACT_TANH, int(self.residual), _lib.ptr(W1),
+                                                _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), _lib.ptr(x0), _lib.ptr(ud),
+                                                _lib.ptr(x), _lib.ptr(F), _lib.ptr(f), _lib.stream_ptr(d))
+        _lib.check(rc, "dmpc_mlp_rollout_linearize")
+        return x.to(x_init.dtype), (None if F is None else F.to(x_init.dtype)), (None if f is None else f.to(x_init.dtype))
+
+    def _rollout_linearize_torch(self, x_init, u, want_model):
+        T = u.shape[0]
+        xs, Fs, fs = [x_init], [], []
+        for t in range(T - 1):
+            a = self._hidden(xs[t], u[t])
+            nxt = self._output(a, xs[t])
+            if want_model:
+                Fs.append(self._jacobian(a))
+                fs.append(nxt - bmv(Fs[t], torch.cat((xs[t], u[t]), dim=1)))
+            xs.append(nxt)
+        x = torch.stack(xs, 0)
+        if not want_model:
+            return x, None, None
+        if T == 1:
+            return x, x.new_zeros((0,) + tuple(x_init.shape) + (self.n_state + self.n_ctrl,)), x.new_zeros((0,) + tuple(x_init.shape))
+        return x, torch.stack(Fs, 0), torch.stack(fs, 0)
+
+    def linearize(self, x, u):
+        """F_t = d next / d [x;u], f_t = next - F_t [x_t;u_t] along the trajectory re-rolled from x[0] (the contract of
+        `PendulumDx.linearize`).  No gradient wanted: all of it from the kernel.  Otherwise F still comes from the kernel on
+        the GPU, next and the re-rolled states from a live torch rollout."""
+        T = x.shape[0]
+        x0 = x[0]
+        if self.fused_ok(x0, u):
+            _, F, f = self.rollout_linearize(x0, u)
+            return F, f
+        if not self._grad_wanted(x0, u):
+            _, F, f = self._rollout_linearize_torch(x0, u, True)
+            return F, f
+        F_dev = None
+        if self._on_device(x0, u):
+            F_dev = self.rollout_linearize(x0, u)[1]
+        xs, Fs, fs = [x0], [], []
+        for t in range(T - 1):
+            xt, ut = xs[t], u[t]
+            a = self._hidden(xt, ut)
+            nxt = self._output(a, xt)
+            Ft = F_dev[t] if F_dev is not None else self._jacobian(a)
+            Fs.append(Ft)
+            fs.append(nxt - bmv(Ft, torch.cat((xt, ut), dim=1)))
+            xs.append(nxt)
+        if T == 1:
+            _, F, f = self._rollout_linearize_torch(x0.detach(), u.detach(), True)
+            return F, f
+        return torch.stack(Fs, 0), torch.stack(fs, 0)

@@ -83,6 +83,12 @@ def _is_simple_pendulum(dyn):
     return isinstance(dyn, PendulumDx) and dyn.simple
 
 
+def _is_device_mlp(dyn, nx, nu):
+    """MlpDx with the step's dimensions, of a size the kernels serve"""
+    from .mlp_dx import MlpDx
+    return isinstance(dyn, MlpDx) and (dyn.n_state, dyn.n_ctrl) == (nx, nu) and dyn.supported()
+
+
 def du_norm(u_old, u_new, scrambled=True):
     du = u_old - u_new
     T, B, nu = du.shape
@@ -380,6 +386,27 @@ class MPCstep:
                     _lib.ptr(costs), _lib.ptr(old), _lib.ptr(alphas), _lib.ptr(objs), _lib.ptr(u1), _lib.ptr(nls),
                     _lib.ptr(info), _lib.stream_ptr(d))
             _lib.check(rc, "dmpc_mpc_forward_rec_pendulum")
+            raise_info(info, "MPCstep.forward_rec")
+        elif isinstance(true_cost, QuadCost) and _is_device_mlp(true_dynamics, nx, nu):
+            # a learned one-hidden-layer network evaluated inside the kernel's line search (mpc_step.py:237-240); its weights
+            # go in as device pointers
+            lib = _lib.load()
+            Ct, ct = _lib.f32c(_as_tensor(true_cost.C), d), _lib.f32c(_as_tensor(true_cost.c), d)
+            W1, b1, W2, b2 = true_dynamics.device_weights(d)
+            f32 = dict(dtype=torch.float32, device=d)
+            x, u, u1 = torch.empty((T, B, nx), **f32), torch.empty((T, B, nu), **f32), torch.empty((T, B, nu), **f32)
+            costs, old, alphas = torch.empty((B,), **f32), torch.empty((B,), **f32), torch.empty((B,), **f32)
+            objs = torch.empty((T, B), **f32)
+            nls = torch.empty((B,), dtype=torch.int32, device=d)
+            info = torch.zeros(B, dtype=torch.int32, device=d)
+            with _lib.guard(d):
+                rc = lib.dmpc_mpc_forward_rec_mlp(
+                    T, B, nx, nu, true_dynamics.n_hidden, 0, int(true_dynamics.residual), _lib.ptr(W1), _lib.ptr(b1),
+                    _lib.ptr(W2), _lib.ptr(b2), _lib.ptr(Kd), _lib.ptr(kd), _lib.ptr(self._u), _lib.ptr(self._xs),
+                    _lib.ptr(self._lo), _lib.ptr(self._hi), _lib.ptr(Ct), _lib.ptr(ct), float(ls_decay), int(max_ls_iter),
+                    _lib.ptr(x), _lib.ptr(u), _lib.ptr(costs), _lib.ptr(old), _lib.ptr(alphas), _lib.ptr(objs), _lib.ptr(u1),
+                    _lib.ptr(nls), _lib.ptr(info), _lib.stream_ptr(d))
+            _lib.check(rc, "dmpc_mpc_forward_rec_mlp")
             raise_info(info, "MPCstep.forward_rec")
         else:
             x, u, u1, costs, alphas, objs, nls = self._forward_rec_callable(Kd, kd, true_cost, true_dynamics,

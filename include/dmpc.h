@@ -298,6 +298,34 @@ int dmpc_pendulum_rollout_linearize(int T, int B, const float *x_init, const flo
                                     float dt, float max_torque, int clamp_grad_closed, float *x_out, float *F_out,
                                     float *f_out, dmpc_stream_t stream);
 
+/* A learned one-hidden-layer dynamics model (MlpDx of the Python layer) as the true dynamics:
+ *     next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual != 0)
+ * W1 [n_hidden,ns], b1 [n_hidden], W2 [nx,n_hidden], b2 [nx] are DEVICE arrays read by every launch - nothing is cached,
+ * an optimiser step in place is seen by the next call.  `act` is a plain int: 0 = tanh, anything else
+ * DMPC_E_UNSUPPORTED.  Sizes: nx <= 16, nu <= 8, 1 <= n_hidden <= 256, else DMPC_E_UNSUPPORTED (a NULL pointer or a
+ * non-positive T, B, nx, nu: DMPC_E_BADARG; both before any HIP call, dmpc_mlp_dx_supported launches nothing); also
+ * DMPC_E_UNSUPPORTED where an output array would reach 2^31 elements.  One wavefront per trajectory, the weights in LDS,
+ * and ONE step function for both entry points: the states of dmpc_mlp_rollout_linearize and the candidates of the
+ * search are bit-equal for equal controls, whatever B is.
+ *
+ * dmpc_mlp_rollout_linearize: get_traj (util.py:239-277) and linearize_dynamics (mpc/approximate.py:77-119, there by
+ *   chainer.grad) in one launch: x_0 = x_init, x_{t+1} = next(x_t, u_t), F_t = [I|0] residual + W2 diag(1 - a_t^2) W1,
+ *   f_t = x_{t+1} - F_t [x_t;u_t].  x_out [T,B,nx]; F_out [T-1,B,nx,ns] or NULL; f_out [T-1,B,nx] or NULL (NULL with F_out
+ *   NULL).  T = 1: x_out = x_init, nothing else is written.
+ * dmpc_mpc_forward_rec_mlp: dmpc_mpc_forward_rec (its arguments, outputs, per-trajectory termination, bound snap, test on the
+ *   cost difference, cap of 64 passes with DMPC_INFO_LS_ITERCAP, DMPC_INFO_NONFINITE) with the network in place of
+ *   F_true, f_true. */
+int dmpc_mlp_dx_supported(int nx, int nu, int n_hidden, int act);
+int dmpc_mlp_rollout_linearize(int T, int B, int nx, int nu, int n_hidden, int act, int residual, const float *W1,
+                               const float *b1, const float *W2, const float *b2, const float *x_init, const float *u,
+                               float *x_out, float *F_out, float *f_out, dmpc_stream_t stream);
+int dmpc_mpc_forward_rec_mlp(int T, int B, int nx, int nu, int n_hidden, int act, int residual, const float *W1,
+                             const float *b1, const float *W2, const float *b2, const float *Ks, const float *ks,
+                             const float *controls, const float *states, const float *u_lower, const float *u_upper,
+                             const float *C_true, const float *c_true, float ls_decay, int max_ls_iter, float *x_out,
+                             float *u_out, float *costs, float *old_costs, float *alphas, float *objs, float *u_first,
+                             int32_t *n_ls_iter, int32_t *info, dmpc_stream_t stream);
+
 /* Nominal rollout under a LinDx (util.py:239-277 get_traj): x_0 = x_init, x_{t+1} = F_t [x_t; u_t] + f_t (f may be
  * NULL), with the summation order of the MPC step's own line-search rollout - so that a trajectory re-rolled from
  * unchanged controls reproduces the nominal one bit for bit and the box-DDP stop test sees du = 0 at a fixed point. */

@@ -120,6 +120,27 @@ int main() {
     EXPECT(dmpc_mpc_step_backward(20, 4, 8, 2, p, p, p, p, p, p, p, p, p, p, nullptr, nullptr, nullptr, nullptr, p, p, nullptr,
                                   nullptr, 0.f, ws, mwb, pi, nullptr) != DMPC_E_UNSUPPORTED);
   }
+  // the learned dynamics model: size and argument checks come before any HIP call; the supported sizes go on to the launch
+  for (int nx : {0, 1, 3, 16, 17})
+    for (int nu : {0, 1, 8, 9})
+      for (int H : {0, 1, 5, 64, 256, 257})
+        for (int act : {0, 1})
+          for (int T : {0, 1, 2, 20}) {
+            const bool sized = nx > 0 && nu > 0, ok = sized && act == 0 && nx <= 16 && nu <= 8 && H >= 1 && H <= 256;
+            EXPECT(dmpc_mlp_dx_supported(nx, nu, H, act) == (ok ? 1 : 0));
+            const int rr = dmpc_mlp_rollout_linearize(T, 5, nx, nu, H, act, 1, p, p, p, p, p, p, p, p, p, nullptr);
+            const int rs = dmpc_mpc_forward_rec_mlp(T, 5, nx, nu, H, act, 1, p, p, p, p, p, p, p, p, p, p, p, p, 0.2f, 10, p, p, p, p,
+                                                    p, p, p, pi, pi, nullptr);
+            if (!sized || T <= 0) EXPECT(rr == DMPC_E_BADARG && rs == DMPC_E_BADARG);
+            else if (!ok) EXPECT(rr == DMPC_E_UNSUPPORTED && (T == 1 ? rs == DMPC_E_BADARG : rs == DMPC_E_UNSUPPORTED));
+            else EXPECT(rr >= 0 && (T == 1 ? rs == DMPC_E_BADARG : rs >= 0));
+            if (ok && T > 1) {
+              EXPECT(dmpc_mlp_rollout_linearize(T, 5, nx, nu, H, 0, 1, nullptr, p, p, p, p, p, p, p, p, nullptr) == DMPC_E_BADARG);
+              EXPECT(dmpc_mlp_rollout_linearize(T, 5, nx, nu, H, 0, 1, p, p, p, p, p, p, p, nullptr, p, nullptr) == DMPC_E_BADARG);
+              EXPECT(dmpc_mpc_forward_rec_mlp(T, 5, nx, nu, H, 0, 1, p, p, p, p, p, p, p, nullptr, p, p, p, p, 0.2f, 10, p, p, p, p,
+                                              p, p, p, pi, pi, nullptr) == DMPC_E_BADARG);
+            }
+          }
   EXPECT(dmpc_lqr_shared_workspace_bytes(0, 1, 1, 1) == 0 && dmpc_lqr_shared_saved_bytes(0, 1, 1) == 0);
   EXPECT(dmpc_lqr_kernel_family(0, 3) == DMPC_E_UNSUPPORTED);
   EXPECT(dmpc_lqr_workspace_bytes(0, 1, 1, 1) == 0);

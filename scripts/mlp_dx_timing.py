@@ -1,0 +1,95 @@
+"""One `BoxDDP` solve under a learned one-hidden-layer dynamics model, two ways in the same run:
+  device   - the `MlpDx` module itself: rollout + linearisation in one launch, the line search inside its kernel;
+  callable - the same module behind `lambda x, u: m(x, u)`: `linearize_dynamics` through torch.autograd and the line search
+             as torch ops around the callable - the route every non-linear dynamics took before `MlpDx` (the baseline).
+Medians over `--iters` solves after warm-up (device events around the whole solve, host time included), the number of
+kernel launches of one solve of each, and how far the two solutions' costs are apart.
+
+    python scripts/mlp_dx_timing.py [--iters 20] [--warmup 3] [--cases 3x1x32,8x2x64] [--batch 128] [--horizon 20] [--json out]"""
+import argparse
+import json
+import os
+import sys
+import warnings
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from chainer_differentiable_mpc_amd import BoxDDP, MlpDx, QuadCost, synthetic  # noqa: E402
+
+
+def median_ms(fn, iters, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    ts.sort()
+    return ts[len(ts) // 2]
+
+
+def count_launches(fn):
+    """kernel launches of one call, as the profiler sees them (None where it records no device activity)"""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if str(e.device_type).endswith("CUDA") and "memcpy" not in e.name.lower()
+                and "memset" not in e.name.lower())
+        return n or None
+    except Exception:       # a build without the device tracer
+        return None
+
+
+def run_case(nx, nu, H, B, T, iters, warmup):
+    p = synthetic.make_lqr_problem(B, T, nx, nu, seed=1)
+    dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device="cuda")   # noqa: E731
+    x0, cost = dev(p["x_init"]), QuadCost(dev(p["C"]), dev(p["c"]))
+    m = MlpDx(nx, nu, H, seed=0).cuda()
+    out = dict(nx=nx, nu=nu, n_hidden=H, B=B, T=T)
+    sols = {}
+    for tag, dyn in (("device", m), ("callable", lambda x, u: m(x, u))):
+        solver = BoxDDP(T, -0.5, 0.5, B, nx, nu, None, max_iter=10, quiet=True)
+
+        def solve():
+            with torch.no_grad(), warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                sols[tag] = solver((x0, cost, dyn))
+        out[tag + "_ms"] = median_ms(solve, iters, warmup)
+        out[tag + "_launches"] = count_launches(solve)
+        out[tag + "_n_iter"], out[tag + "_status"] = solver.n_iter, solver.status
+    out["speedup"] = out["callable_ms"] / out["device_ms"]
+    cd, cc = sols["device"][2], sols["callable"][2]
+    out["costs_max_rel_diff"] = float(((cd - cc).abs() / cc.abs().clamp(min=1.0)).max())
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--cases", default="3x1x32,8x2x64")
+    ap.add_argument("--batch", type=int, default=128)
+    ap.add_argument("--horizon", type=int, default=20)
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    res = []
+    for c in a.cases.split(","):
+        nx, nu, H = (int(v) for v in c.split("x"))
+        r = run_case(nx, nu, H, a.batch, a.horizon, max(a.iters, 20), a.warmup)
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
