@@ -26,219 +26,252 @@ constexpr size_t kGainLdsBudget = 156 * 1024;   // (round 4: was 64 KB - (8,4) a
 constexpr int kDmaDepthB = DMPC_DMA_DEPTH_B, kDmaDepthF = DMPC_DMA_DEPTH_F;
 constexpr size_t kDmaLdsBudget = 156 * 1024;
 constexpr size_t kAsmLdsBudget = 160 * 1024;
-// the path (dmpc.h: DMPC_LQR_PATH_*) of a plain solve at a shape with a specialisation of its own
-template <int NX, int NU, int L>
-static int solve_path(int T, int B) {
-  if constexpr (L == 16 && LqrAsm<NX, NU, false, false>::kAvailable) {
-    if (B >= 4 && T >= 2 && !knob_on<Knob::DMPC_NO_ASM>()) {
-      if constexpr (LqrAsm<NX, NU, false, true>::kAvailable) {
-        if (T <= LqrAsm<NX, NU, false, true>::NSTASH && lqr_asm_lds_bytes<NX, NU, true>(T) <= kAsmLdsBudget &&
-            !knob_on<Knob::DMPC_NO_STASH>())
-          return DMPC_LQR_PATH_ASM_STASH;
-      }
-      if (lqr_asm_lds_bytes<NX, NU, false>(T) <= kAsmLdsBudget) return DMPC_LQR_PATH_ASM_RING;
-      if constexpr (LqrAsm<NX, NU, false, false, false, true>::kAvailable) {
-        if (lqr_asm_lds_bytes<NX, NU, false, false, true>(T) <= kAsmLdsBudget) return DMPC_LQR_PATH_ASM_WS;
-      }
-    }
-  }
-  if constexpr (L == 16) {
-    using Lay = LqrDmaLayout<NX, NU, kDmaDepthB, kDmaDepthF>;
-    if (B >= 4 && T >= 2 && Lay::lds_bytes(T) <= kDmaLdsBudget && !knob_on<Knob::DMPC_NO_DMA>()) return DMPC_LQR_PATH_DMA;
-  }
-  if constexpr (L == 64 && NX % 4 == 0 && NU % 4 == 0) {
-    if (!knob_on<Knob::DMPC_NO_WAVE_MFMA>()) return DMPC_LQR_PATH_WAVE_MFMA;
-  }
-  return DMPC_LQR_PATH_PREFETCH;
-}
-// the generated stream with its gain rows in LDS, with or without the F stash
-static bool asm_lds_path(int path) { return path == DMPC_LQR_PATH_ASM_RING || path == DMPC_LQR_PATH_ASM_STASH; }
 
-// the saving solve: the stash form of the generated stream with room in LDS for the staging area of the saved blocks
-template <int NX, int NU, int L>
-static int saving_available(int T, int B) {
-  if constexpr (L == 16 && LqrAsm<NX, NU, true, true, false, false, true>::kAvailable)
-    return solve_path<NX, NU, L>(T, B) == DMPC_LQR_PATH_ASM_STASH &&
-           lqr_asm_lds_bytes<NX, NU, true, true>(T) <= kAsmLdsBudget;
-  return 0;
+// ---- One launcher per kernel template.  A launcher reads from the call only what is an argument form of its kernel (f absent,
+// gains wanted, the mask); which kernel takes a call is lqr_route's business alone.
+
+// the generated instruction stream (lqr_asm_kernel.hpp) in one of its forms
+template <int NX, int NU, bool STASH, bool MASKED = false, bool GHBM = false, bool SAVE = false, bool AFFINE = false,
+          bool ADJ = false>
+static int launch_asm(const LqrArgs &a, hipStream_t stream) {
+  return with_bools([&](auto has_f, auto write_k) {
+    constexpr bool HAS_F = decltype(has_f)::value, WRITE_K = decltype(write_k)::value;
+    if constexpr (LqrAsm<NX, NU, WRITE_K, STASH, MASKED, GHBM, SAVE, AFFINE, ADJ>::kAvailable && !(AFFINE && HAS_F))
+      return launch_kernel(lqr_asm_kernel<NX, NU, HAS_F, WRITE_K, STASH, MASKED, GHBM, SAVE, AFFINE, ADJ>, four_traj_per_wave_grid(a.B),
+                           dim3(256), lqr_asm_lds_bytes<NX, NU, STASH, SAVE, GHBM>(a.T), stream, a);
+    else
+      return (int)DMPC_E_UNSUPPORTED;   // (no such stream: the route does not send the call here)
+  }, a.f != nullptr, a.Ks != nullptr);
+}
+// ... with the F stash where the route asks for it and the form has one; nullptr: the shape has no stream of this form
+template <int NX, int NU, bool STASH, bool MASKED, bool GHBM, bool SAVE, bool AFFINE, bool ADJ>
+constexpr bool kAsmForm = LqrAsm<NX, NU, false, STASH, MASKED, GHBM, SAVE, AFFINE, ADJ>::kAvailable ||
+                          LqrAsm<NX, NU, true, STASH, MASKED, GHBM, SAVE, AFFINE, ADJ>::kAvailable;   // (with or without gains out)
+template <int NX, int NU, bool MASKED = false, bool GHBM = false, bool SAVE = false, bool AFFINE = false, bool ADJ = false>
+static LqrLauncher asm_launcher(bool stash) {
+  if constexpr (kAsmForm<NX, NU, true, MASKED, GHBM, SAVE, AFFINE, ADJ>) {
+    if (stash) return launch_asm<NX, NU, true, MASKED, GHBM, SAVE, AFFINE, ADJ>;
+  }
+  if constexpr (kAsmForm<NX, NU, false, MASKED, GHBM, SAVE, AFFINE, ADJ>)
+    return launch_asm<NX, NU, false, MASKED, GHBM, SAVE, AFFINE, ADJ>;
+  return nullptr;
 }
 
+// the LDS-DMA ring kernel (lqr_dma_kernel.hpp); KHBM: its gain rows through the workspace
+template <int NX, int NU, bool KHBM>
+static int launch_dma(const LqrArgs &a, hipStream_t stream) {
+  return launch_kernel(lqr_dma_kernel<NX, NU, kDmaDepthB, kDmaDepthF, KHBM>, four_traj_per_wave_grid(a.B), dim3(256),
+                       LqrDmaLayout<NX, NU, kDmaDepthB, kDmaDepthF, KHBM>::lds_bytes(a.T), stream, a);
+}
+
+// lqr_kernel (lqr_kernels.hpp): a lane group per trajectory.  K_LDS: the gains of a solve stay in LDS; else they pass through
+// HBM - the caller's arrays, else the workspace.  PAD: a container
 template <int NX, int NU, int L>
-static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
+constexpr size_t group_gain_bytes(int T) { return (size_t)(256 / L) * T * NU * (NX + 1) * sizeof(float); }
+template <int NX, int NU, int L, int MODE, bool K_LDS, bool PAD>
+static int launch_group(const LqrArgs &a0, hipStream_t stream) {
   constexpr int GPB = 256 / L;
-  const dim3 grid((a.B + GPB - 1) / GPB), block(256);
-  const bool masked = a.mask != nullptr;
-  const size_t lds_gain = (size_t)GPB * a.T * NU * (NX + 1) * sizeof(float);
-#define DMPC_LAUNCH(MASKED, MODE, KLDS, SHMEM) \
-  DMPC_LAUNCH_GGL((lqr_kernel<NX, NU, L, MASKED, MODE, KLDS>), grid, block, SHMEM, stream, a)
-  if (a.Vv_in == nullptr && (a.c_u != nullptr || (a.x_init == nullptr && a.x != nullptr))) {
-    // c in two arrays / x_init = 0: forms only the generated streams take (lqr_second_solve below)
-    bool ok = false;
-    if constexpr (L == 16 && LqrAsm<NX, NU, false, false>::kAvailable)
-      ok = mode == kSolve && !masked && a.Ks == nullptr && asm_lds_path(solve_path<NX, NU, L>(a.T, a.B));
-    if (!ok) return DMPC_E_UNSUPPORTED;
-  }
-  if (a.Vv_in != nullptr) {
-    // DiffLqr.backward in one launch (lqr_adjoint below): the affine re-solve whose rollout writes the gradients
-    if constexpr (L == 16 && LqrAsm<NX, NU, false, true, false, false, false, true, true>::kAvailable) {
-      if (mode == kSolve && !masked && a.f == nullptr && a.Ks == nullptr && a.Ks_in != nullptr &&
-          solve_path<NX, NU, L>(a.T, a.B) == DMPC_LQR_PATH_ASM_STASH) {
-        const int waves = (a.B + 3) / 4;
-        const size_t shmem = lqr_asm_lds_bytes<NX, NU, true>(a.T);
-        DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, false, true, false, false, false, true, true>), dim3((waves + 3) / 4),
-                        block, shmem, stream, a);
-        return (int)hipGetLastError();
-      }
-    }
-    return DMPC_E_UNSUPPORTED;
-  }
-  if (a.Ks_in != nullptr) {
-    // the re-solve from saved gains (dmpc_lqr_saved_solve): the affine form of the generated stream, F in the stash
-    if constexpr (L == 16 && LqrAsm<NX, NU, false, true, false, false, false, true>::kAvailable) {
-      if (mode == kSolve && !masked && a.f == nullptr && a.Ks == nullptr &&
-          solve_path<NX, NU, L>(a.T, a.B) == DMPC_LQR_PATH_ASM_STASH) {
-        const int waves = (a.B + 3) / 4;
-        const size_t shmem = lqr_asm_lds_bytes<NX, NU, true>(a.T);
-        DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, false, true, false, false, false, true>), dim3((waves + 3) / 4),
-                           block, shmem, stream, a);
-        return (int)hipGetLastError();
-      }
-    }
-    return DMPC_E_UNSUPPORTED;
-  }
+  LqrArgs a = a0;
+  if (!K_LDS && a.Ks == nullptr) { a.Ks = a.wsK; a.ks = a.wsk; }
+  return with_bools([&](auto masked) {
+    return launch_kernel(lqr_kernel<NX, NU, L, decltype(masked)::value, MODE, K_LDS, PAD>, dim3((a.B + GPB - 1) / GPB), dim3(256),
+                         K_LDS ? group_gain_bytes<NX, NU, L>(a.T) : 0, stream, a);
+  }, a.mask != nullptr);
+}
+
+// the wide row kernel (lqr_wide_kernel.hpp); PAD: a container
+template <int NX, int NU, bool PAD>
+static int launch_wide(const LqrArgs &a, hipStream_t stream) {
+  constexpr int DB = 2, DF = 2;
+  constexpr size_t lds = LqrWideLayout<NX, NU, DB, DF>::lds_bytes();
+  static_assert(lds <= 160 * 1024, "rings beyond a CU's LDS");
+  return with_bools([&](auto masked) {
+    return launch_kernel_big_lds(lqr_wide_kernel<NX, NU, DB, DF, PAD, decltype(masked)::value>, dim3((a.B + 15) / 16), dim3(256),
+                                 lds, stream, a);
+  }, a.mask != nullptr);
+}
+
+// the runtime-dimension kernels: their launchers (lqr_generic.hpp, lqr_tiled.hpp) take the mode and the sizes as arguments
+template <int MODE>
+static int launch_generic(const LqrArgs &a, hipStream_t stream) { return launch_lqr_generic(MODE, a.nx_log, a.nu_log, a, stream); }
+template <int MODE>
+static int launch_tiled(const LqrArgs &a, hipStream_t stream) {
+  return launch_lqr_tiled(MODE, a.nx_log, a.nu_log, a, a.tiled_scratch, stream);
+}
+static LqrLauncher by_mode(int mode, LqrLauncher solve, LqrLauncher backward, LqrLauncher forward) {
+  return mode == kSolve ? solve : mode == kBackwardOnly ? backward : forward;
+}
+
+// ---- The order of the code object.  The compiler emits the kernels in the order the translation unit first names them, and
+// the generated (8,2) stream runs 6 % slower at another offset of the code object (profiles/r05/lqr_dispatch_refactor_ab.txt).
+// These functions name the kernels whose first mention the launchers above would move, in the order the code object has
+// had; nothing calls them (route_exact and wide_exact_launcher mention them), and the route names what is left in that order by itself.
+template <class... K>
+static void name_kernels(K...) {}
+template <int NX, int NU, int L>
+static void kernel_order() {
   if constexpr (L == 16 && LqrAsm<NX, NU, false, false>::kAvailable) {
-    // fastest path: the whole solve as one generated instruction stream (lqr_asm_kernel.hpp); with the F stash
-    // (no second read of F) when the horizon fits the stash registers
-    const int path = solve_path<NX, NU, L>(a.T, a.B);
-    if constexpr (LqrAsm<NX, NU, false, false, true>::kAvailable) {
-      // LQR_active on the generated stream: same paths, flags fetched as dwords (B * nu must be a multiple of 4)
-      if (mode == kSolve && masked && a.Ks == nullptr && (a.B * NU) % 4 == 0 && (reinterpret_cast<uintptr_t>(a.mask) & 3u) == 0 &&
-          asm_lds_path(path)) {
-        const int waves = (a.B + 3) / 4;
-        const dim3 g((waves + 3) / 4);
-        const bool has_f = a.f != nullptr;
-#define DMPC_ASM_LAUNCH_M(STASH)                                                                                        \
-  do {                                                                                                                  \
-    const size_t shmem = lqr_asm_lds_bytes<NX, NU, STASH>(a.T);                                                         \
-    if (has_f) DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, true, false, STASH, true>), g, block, shmem, stream, a);      \
-    else DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, false, STASH, true>), g, block, shmem, stream, a);           \
-    return (int)hipGetLastError();                                                                                      \
-  } while (0)
-        if constexpr (LqrAsm<NX, NU, false, true, true>::kAvailable) {
-          if (path == DMPC_LQR_PATH_ASM_STASH) DMPC_ASM_LAUNCH_M(true);
-        }
-        DMPC_ASM_LAUNCH_M(false);
-#undef DMPC_ASM_LAUNCH_M
-      }
+    if constexpr (LqrAsm<NX, NU, false, true, false, false, false, true, true>::kAvailable)
+      name_kernels(lqr_asm_kernel<NX, NU, false, false, true, false, false, false, true, true>);
+    if constexpr (LqrAsm<NX, NU, false, true, false, false, false, true>::kAvailable)
+      name_kernels(lqr_asm_kernel<NX, NU, false, false, true, false, false, false, true>);
+    if constexpr (LqrAsm<NX, NU, false, true, true>::kAvailable)
+      name_kernels(lqr_asm_kernel<NX, NU, true, false, true, true>, lqr_asm_kernel<NX, NU, false, false, true, true>);
+    if constexpr (LqrAsm<NX, NU, false, false, true>::kAvailable)
+      name_kernels(lqr_asm_kernel<NX, NU, true, false, false, true>, lqr_asm_kernel<NX, NU, false, false, false, true>);
+    name_kernels(lqr_asm_kernel<NX, NU, true, true, false>, lqr_asm_kernel<NX, NU, false, true, false>);
+    if constexpr (LqrAsm<NX, NU, false, false, false, true>::kAvailable)
+      name_kernels(lqr_asm_kernel<NX, NU, true, false, false, false, true>, lqr_asm_kernel<NX, NU, false, false, false, false, true>);
+    if constexpr (LqrAsm<NX, NU, false, true>::kAvailable) {
+      if constexpr (LqrAsm<NX, NU, true, true, false, false, true>::kAvailable)
+        name_kernels(lqr_asm_kernel<NX, NU, true, true, true, false, false, true>,
+                     lqr_asm_kernel<NX, NU, false, true, true, false, false, true>);
+      name_kernels(lqr_asm_kernel<NX, NU, true, false, true>, lqr_asm_kernel<NX, NU, true, true, true>,
+                   lqr_asm_kernel<NX, NU, false, false, true>, lqr_asm_kernel<NX, NU, false, true, true>);
     }
-    if (mode == kBackwardOnly && !masked && asm_lds_path(path) && lqr_asm_lds_bytes<NX, NU, false>(a.T) <= kAsmLdsBudget) {
-      // LqrRecursion.backward(): the generated stream's backward sweep with the gains written to HBM (x == nullptr)
-      const int waves = (a.B + 3) / 4;
-      const size_t shmem = lqr_asm_lds_bytes<NX, NU, false>(a.T);
-      if (a.f != nullptr)
-        DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, true, true, false>), dim3((waves + 3) / 4), block, shmem, stream, a);
-      else
-        DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, true, false>), dim3((waves + 3) / 4), block, shmem, stream, a);
-      return (int)hipGetLastError();
+    if constexpr (LqrAsm<NX, NU, true, false, false, false, true>::kAvailable)
+      name_kernels(lqr_asm_kernel<NX, NU, true, true, false, false, false, true>,
+                   lqr_asm_kernel<NX, NU, false, true, false, false, false, true>);
+    name_kernels(lqr_asm_kernel<NX, NU, true, false, false>, lqr_asm_kernel<NX, NU, false, false, false>);
+  }
+  if constexpr (L == 16)
+    name_kernels(lqr_dma_kernel<NX, NU, kDmaDepthB, kDmaDepthF, false>, lqr_kernel<NX, NU, L, true, kSolve, true, false>,
+                 lqr_kernel<NX, NU, L, false, kSolve, true, false>, lqr_dma_kernel<NX, NU, kDmaDepthB, kDmaDepthF, true>);
+}
+
+// ---- The route: which kernel takes a call.  It launches nothing and dereferences nothing; dispatch_lqr and the queries of
+// the C ABI (dmpc_lqr_solve_path, dmpc_lqr_saving_available) all ask it, so what a caller is told is what runs.
+
+// The form of a call, set by the entry point that builds it (the generated streams alone take the last four).
+enum class LqrForm {
+  kPlain,
+  kMasked,    // LQR_active: a.mask
+  kSplitC,    // DiffLqr.backward's second solve: c as two arrays (a.c, a.c_u), x_init = 0, f = 0
+  kSaved,     // the affine re-solve from saved gains (a.Ks_in, a.Quu_in, a.Qxu_in)
+  kAdjoint,   // ... whose rollout writes the gradients (a.Vv_in)
+  kSaving     // the training form: Quu, Qxu, [V | v] saved next to the gains
+};
+struct LqrCall {
+  int mode;   // LqrMode
+  LqrForm form;
+  int T, B, nx, nu;
+  bool gains;         // the caller takes the gains (a.Ks, a.ks)
+  bool ws, scratch;   // a workspace for gain rows / the tiled kernel's scratch behind it were given
+  bool mask_dwords;   // the mask can be fetched as dwords: its base is 4-byte aligned
+};
+struct LqrRoute {
+  int path;                                       // DMPC_LQR_PATH_*, or the DMPC_E_* of a refusal
+  LqrLauncher launch = nullptr, then = nullptr;   // then: the second launch of a chain (sweep, then rollout)
+};
+
+// the kernels that give a wavefront four trajectories: at least one whole wavefront, a horizon with an F
+static bool fills_a_wave(int T, int B) { return B >= 4 && T >= 2; }
+// ... and whose stream has no ragged last wavefront (the saving and the affine forms)
+static bool whole_waves(int B) { return B % 4 == 0; }
+// gains that pass through HBM have a place: the caller's arrays, else the workspace
+static bool gains_have_a_place(const LqrCall &q) { return q.gains || q.ws; }
+
+// the form of the generated stream that serves a solve of this size (ASM_STASH, ASM_RING, ASM_WS), or -1
+template <int NX, int NU>
+static int asm_path(int T, int B) {
+  if constexpr (LqrAsm<NX, NU, false, false>::kAvailable) {
+    if (!fills_a_wave(T, B) || knob_on<Knob::DMPC_NO_ASM>()) return -1;
+    if constexpr (LqrAsm<NX, NU, false, true>::kAvailable) {
+      if (T <= LqrAsm<NX, NU, false, true>::NSTASH && lqr_asm_lds_bytes<NX, NU, true>(T) <= kAsmLdsBudget &&
+          !knob_on<Knob::DMPC_NO_STASH>())
+        return DMPC_LQR_PATH_ASM_STASH;
     }
-    const bool plain = mode == kSolve && !masked;
+    if (lqr_asm_lds_bytes<NX, NU, false>(T) <= kAsmLdsBudget) return DMPC_LQR_PATH_ASM_RING;
     if constexpr (LqrAsm<NX, NU, false, false, false, true>::kAvailable) {
-      // long horizons: the gain rows pass through the workspace instead of LDS (the caller's Ks / ks are another layout:
-      // a solve that wants them goes to the kernels below)
-      if (plain && path == DMPC_LQR_PATH_ASM_WS && a.Ks == nullptr && a.wsK != nullptr && a.c_u == nullptr && a.x_init != nullptr) {
-        const int waves = (a.B + 3) / 4;
-        const size_t shmem = lqr_asm_lds_bytes<NX, NU, false, false, true>(a.T);
-        if (a.f != nullptr) DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, true, false, false, false, true>), dim3((waves + 3) / 4), block, shmem, stream, a);
-        else DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, false, false, false, true>), dim3((waves + 3) / 4), block, shmem, stream, a);
-        return (int)hipGetLastError();
-      }
-    }
-    if (plain && asm_lds_path(path)) {
-      const int waves = (a.B + 3) / 4;
-      const dim3 g((waves + 3) / 4);
-      const bool has_f = a.f != nullptr, write_k = a.Ks != nullptr;
-#define DMPC_ASM_LAUNCH(STASH)                                                                                   \
-  do {                                                                                                           \
-    const size_t shmem = lqr_asm_lds_bytes<NX, NU, STASH>(a.T);                                                  \
-    if constexpr (LqrAsm<NX, NU, true, STASH, false, false, true>::kAvailable) {                                 \
-      if (a.Quu_out != nullptr && write_k) { /* training form: Quu, Qxu, [V | v] saved too (staged in LDS) */     \
-        const size_t shmem_s = lqr_asm_lds_bytes<NX, NU, STASH, true>(a.T);                                      \
-        if (shmem_s > kAsmLdsBudget) return DMPC_E_UNSUPPORTED;                                                  \
-        if (has_f) DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, true, true, STASH, false, false, true>), g, block, shmem_s, stream, a); \
-        else DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, true, STASH, false, false, true>), g, block, shmem_s, stream, a); \
-        return (int)hipGetLastError();                                                                           \
-      }                                                                                                          \
-    }                                                                                                            \
-    if (a.Quu_out != nullptr) return DMPC_E_UNSUPPORTED;                                                         \
-    if (has_f && !write_k) DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, true, false, STASH>), g, block, shmem, stream, a); \
-    else if (has_f) DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, true, true, STASH>), g, block, shmem, stream, a); \
-    else if (!write_k) DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, false, STASH>), g, block, shmem, stream, a); \
-    else DMPC_LAUNCH_GGL((lqr_asm_kernel<NX, NU, false, true, STASH>), g, block, shmem, stream, a);           \
-    return (int)hipGetLastError();                                                                               \
-  } while (0)
-      if constexpr (LqrAsm<NX, NU, false, true>::kAvailable) {
-        if (path == DMPC_LQR_PATH_ASM_STASH) DMPC_ASM_LAUNCH(true);
-      }
-      DMPC_ASM_LAUNCH(false);
-#undef DMPC_ASM_LAUNCH
+      if (lqr_asm_lds_bytes<NX, NU, false, false, true>(T) <= kAsmLdsBudget) return DMPC_LQR_PATH_ASM_WS;
     }
   }
+  return -1;
+}
+
+// lqr_kernel by mode; a solve keeps its gains in LDS while they fit (`told`: the path code of the kernel's family)
+template <int NX, int NU, int L, bool PAD>
+static LqrRoute route_group(const LqrCall &q, int told) {
+  if (q.mode == kSolve) {
+    if (group_gain_bytes<NX, NU, L>(q.T) <= kGainLdsBudget) return {told, launch_group<NX, NU, L, kSolve, true, PAD>};
+    if (!gains_have_a_place(q)) return {DMPC_E_WORKSPACE};
+    return {told, launch_group<NX, NU, L, kSolve, false, PAD>};
+  }
+  return {told, by_mode(q.mode, nullptr, launch_group<NX, NU, L, kBackwardOnly, false, PAD>,
+                        launch_group<NX, NU, L, kForwardOnly, false, PAD>)};
+}
+
+// a shape with a specialisation of its own
+template <int NX, int NU, int L>
+static LqrRoute route_exact(const LqrCall &q) {
+  (void)&kernel_order<NX, NU, L>;   // (instantiated first: the order of the code object)
+  const int T = q.T, B = q.B;
+  const bool masked = q.form == LqrForm::kMasked, plain = q.mode == kSolve && q.form == LqrForm::kPlain;
+  const LqrRoute refused{DMPC_E_UNSUPPORTED};
+  if constexpr (L == 16 && LqrAsm<NX, NU, false, false>::kAvailable) {
+    // fastest: the whole solve as one generated instruction stream; with the F stash (no second read of F) when the horizon fits
+    // the stash registers.  ap: the form a plain solve takes.  The stash form's LDS holds the ring form's (one ring per shape,
+    // the f area on top), so a horizon that takes the stash form also fits the ring form's sweep
+    if constexpr (LqrAsm<NX, NU, false, true>::kAvailable)
+      static_assert(lqr_asm_lds_bytes<NX, NU, true>(1) >= lqr_asm_lds_bytes<NX, NU, false>(1),
+                    "the stash form's LDS holds the ring form's");
+    const int ap = asm_path<NX, NU>(T, B);
+    const bool stash = ap == DMPC_LQR_PATH_ASM_STASH, in_lds = stash || ap == DMPC_LQR_PATH_ASM_RING;
+    const bool stash_whole = stash && whole_waves(B);   // what the saving and the affine forms ask for
+    if (q.form == LqrForm::kSaving) {
+      // the stash form alone, with room in LDS for the staging area of the saved blocks.  (asm_launcher also names the ring form
+      // of the saving stream, as the dispatch always has: those instances are compiled and no call reaches them)
+      bool room = false;
+      if constexpr (LqrAsm<NX, NU, true, true, false, false, true>::kAvailable)
+        room = stash_whole && lqr_asm_lds_bytes<NX, NU, true, true>(T) <= kAsmLdsBudget;
+      return room ? LqrRoute{ap, asm_launcher<NX, NU, false, false, true>(stash)} : refused;
+    }
+    if (q.form == LqrForm::kSaved || q.form == LqrForm::kAdjoint) {   // affine streams: F in the stash, whole wavefronts
+      if (!stash_whole) return refused;
+      if constexpr (LqrAsm<NX, NU, false, true, false, false, false, true, true>::kAvailable) {
+        if (q.form == LqrForm::kAdjoint) return {ap, launch_asm<NX, NU, true, false, false, false, true, true>};
+      }
+      if constexpr (LqrAsm<NX, NU, false, true, false, false, false, true>::kAvailable) {
+        if (q.form == LqrForm::kSaved) return {ap, launch_asm<NX, NU, true, false, false, false, true>};
+      }
+      return refused;
+    }
+    if (q.form == LqrForm::kSplitC) return in_lds ? LqrRoute{ap, asm_launcher<NX, NU>(stash)} : refused;
+    if constexpr (LqrAsm<NX, NU, false, false, true>::kAvailable) {
+      // LQR_active on the stream: flags fetched as dwords (B * nu a multiple of 4); the caller's Ks / ks are another layout
+      if (q.mode == kSolve && masked && !q.gains && (B * NU) % 4 == 0 && q.mask_dwords && in_lds)
+        return {ap, asm_launcher<NX, NU, true>(stash)};
+    }
+    // LqrRecursion.backward(): the ring form's sweep with the gains written to HBM (x == nullptr)
+    if (q.mode == kBackwardOnly && !masked && in_lds) return {DMPC_LQR_PATH_ASM_RING, launch_asm<NX, NU, false>};
+    // long horizons: the gain rows pass through the workspace instead of LDS (a solve that wants the gains goes to the kernels below)
+    if (plain && ap == DMPC_LQR_PATH_ASM_WS && !q.gains && q.ws) return {ap, launch_asm<NX, NU, false, false, true>};
+    if (plain && in_lds) return {ap, asm_launcher<NX, NU>(stash)};
+  }
+  if (q.form != LqrForm::kPlain && !masked) return refused;   // (nothing else reads the streams' own argument forms)
   if constexpr (L == 64 && NX % 4 == 0 && NU % 4 == 0) {
-    // large shapes: backward sweep on the matrix cores (lqr_wave_mfma.hpp, its own translation unit; plain and
-    // LQR_active), gains through HBM, then the bandwidth-bound forward-only kernel
-    if (mode != kForwardOnly && !knob_on<Knob::DMPC_NO_WAVE_MFMA>()) {
-      LqrArgs s = a;
-      if (s.Ks == nullptr && s.wsK == nullptr) return DMPC_E_WORKSPACE;
-      // solve_recursion: the wavefront that finished a trajectory's backward sweep rolls it out in the same launch
-      return launch_lqr_wave_mfma_backward(NX, NU, masked, mode == kSolve, s, stream);
+    // large shapes: backward sweep on the matrix cores (lqr_wave_api.hip; plain and LQR_active), gains through HBM; the wavefront
+    // that finished a trajectory's sweep rolls it out in the same launch
+    if (q.mode != kForwardOnly) {
+      if (const LqrLauncher sweep = lqr_wave_exact_launcher(NX, NU, masked, q.mode == kSolve))
+        return gains_have_a_place(q) ? LqrRoute{DMPC_LQR_PATH_WAVE_MFMA, sweep} : LqrRoute{DMPC_E_WORKSPACE};
     }
   }
   if constexpr (L == 16) {
-    // fast path: LDS-DMA staged inputs (lqr_dma_kernel.hpp) - plain solve, at least one full wave of
-    // trajectories, gains + rings within the 160 KB of a CU
-    using Lay = LqrDmaLayout<NX, NU, kDmaDepthB, kDmaDepthF>;
-    if (mode == kSolve && !masked && a.B >= 4 && a.T >= 2 && Lay::lds_bytes(a.T) <= kDmaLdsBudget &&
-        !knob_on<Knob::DMPC_NO_DMA>()) {
-      const int waves = (a.B + 3) / 4;
-      DMPC_LAUNCH_GGL((lqr_dma_kernel<NX, NU, kDmaDepthB, kDmaDepthF>), dim3((waves + 3) / 4), block,
-                         Lay::lds_bytes(a.T), stream, a);
-      return (int)hipGetLastError();
+    // LDS-DMA staged inputs (lqr_dma_kernel.hpp): the plain solve, gains + rings within the LDS of a CU - or, once the gains of
+    // lqr_kernel no longer fit LDS either, with its gain rows through the workspace (its rings alone fit at any horizon).  Measured
+    // against lqr_kernel (profiles/r04/khbm_vs_lqr_kernel.txt): behind it while the gains still fit LDS ((8,4) T = 50: 96 against
+    // 84 us - hence only then), level at T = 100, ahead at T = 200 ((4,4): 221 against 267 us).  (Told as PREFETCH: the path codes
+    // are older than that form)
+    if (plain && fills_a_wave(T, B) && !knob_on<Knob::DMPC_NO_DMA>()) {
+      if (LqrDmaLayout<NX, NU, kDmaDepthB, kDmaDepthF>::lds_bytes(T) <= kDmaLdsBudget)
+        return {DMPC_LQR_PATH_DMA, launch_dma<NX, NU, false>};
+      if (group_gain_bytes<NX, NU, L>(T) > kGainLdsBudget && q.ws && !q.gains &&
+          LqrDmaLayout<NX, NU, kDmaDepthB, kDmaDepthF, true>::lds_bytes(T) <= kDmaLdsBudget)
+        return {DMPC_LQR_PATH_PREFETCH, launch_dma<NX, NU, true>};
     }
   }
-  if (mode == kSolve) {
-    const bool in_lds = lds_gain <= kGainLdsBudget;
-    if (in_lds) {
-      if (masked) DMPC_LAUNCH(true, kSolve, true, lds_gain);
-      else DMPC_LAUNCH(false, kSolve, true, lds_gain);
-    } else {
-      if constexpr (L == 16) {
-        // long horizon: the LDS-DMA kernel with its gain rows through the workspace (its rings alone fit a CU's LDS at any
-        // horizon).  Measured against lqr_kernel (profiles/r04/khbm_vs_lqr_kernel.txt): behind it while the gains still fit
-        // LDS ((8,4) T = 50: 96 against 84 us - hence only here), level at T = 100, ahead at T = 200 ((4,4): 221 against 267 us)
-        using LayK = LqrDmaLayout<NX, NU, kDmaDepthB, kDmaDepthF, true>;
-        if (!masked && a.B >= 4 && a.T >= 2 && a.wsK != nullptr && a.Ks == nullptr && LayK::lds_bytes(a.T) <= kDmaLdsBudget &&
-            !knob_on<Knob::DMPC_NO_DMA>()) {
-          const int waves = (a.B + 3) / 4;
-          DMPC_LAUNCH_GGL((lqr_dma_kernel<NX, NU, kDmaDepthB, kDmaDepthF, true>), dim3((waves + 3) / 4), block,
-                             LayK::lds_bytes(a.T), stream, a);
-          return (int)hipGetLastError();
-        }
-      }
-      LqrArgs s = a;  // long horizon: gains go through HBM (caller's Ks/ks, else the workspace)
-      if (s.Ks == nullptr) { s.Ks = s.wsK; s.ks = s.wsk; }
-      if (s.Ks == nullptr) return DMPC_E_WORKSPACE;
-      if (masked) DMPC_LAUNCH_GGL((lqr_kernel<NX, NU, L, true, kSolve, false>), grid, block, 0, stream, s);
-      else DMPC_LAUNCH_GGL((lqr_kernel<NX, NU, L, false, kSolve, false>), grid, block, 0, stream, s);
-    }
-  } else if (mode == kBackwardOnly) {
-    if (masked) DMPC_LAUNCH(true, kBackwardOnly, false, 0);
-    else DMPC_LAUNCH(false, kBackwardOnly, false, 0);
-  } else {
-    if (masked) DMPC_LAUNCH(true, kForwardOnly, false, 0);
-    else DMPC_LAUNCH(false, kForwardOnly, false, 0);
-  }
-#undef DMPC_LAUNCH
-  return (int)hipGetLastError();
+  return route_group<NX, NU, L, false>(q, DMPC_LQR_PATH_PREFETCH);
 }
 
 // quick single-shape builds for kernel experiments (scripts/*variants.sh): no containers, and no wide kernels unless
@@ -292,77 +325,42 @@ static int launch_lqr(int mode, const LqrArgs &a, hipStream_t stream) {
 /* ((8,4) as a one-register instance of the same kernel - the template takes it - measured 94 us against lqr_kernel's 84: not used) */
 #endif
 #define DMPC_LQR_WIDE_CONTAINERS(X) X(12, 4) X(16, 4) X(12, 8) X(16, 8)   /* fewest columns first */
-static bool wide_shape(int nx, int nu) {
-#define X(NX_, NU_) \
-  if (nx == NX_ && nu == NU_) return true;
+// (kernel_order above: the wide kernels, plain before LQR_active)
+[[maybe_unused]] static void kernel_order_wide() {
+#define X(NX_, NU_) name_kernels(lqr_wide_kernel<NX_, NU_, 2, 2, false, false>, lqr_wide_kernel<NX_, NU_, 2, 2, false, true>);
   DMPC_LQR_WIDE_SHAPES(X)
 #undef X
-  return false;
+#define X(NX_, NU_) name_kernels(lqr_wide_kernel<NX_, NU_, 2, 2, true, false>, lqr_wide_kernel<NX_, NU_, 2, 2, true, true>);
+  DMPC_LQR_WIDE_CONTAINERS(X)
+#undef X
+}
+static LqrLauncher wide_exact_launcher(int nx, int nu) {
+#define X(NX_, NU_) \
+  if (nx == NX_ && nu == NU_) return launch_wide<NX_, NU_, false>;
+  DMPC_LQR_WIDE_SHAPES(X)
+#undef X
+  return nullptr;
 }
 // ... and, padded by its reads (lqr_wide_kernel<..., PAD>), of every other shape with at most 16 states and 8 controls that has
 // no 16-lane container (nx + nu >= 16): smallest instance first.  Before, all of them took a wavefront per trajectory.
 static bool wide_container_shape(int nx, int nu) {
-  return nx >= 1 && nu >= 1 && nx <= 16 && nu <= 8 && nx + nu >= 16 && !wide_shape(nx, nu);
+  return nx >= 1 && nu >= 1 && nx <= 16 && nu <= 8 && nx + nu >= 16 && wide_exact_launcher(nx, nu) == nullptr;
 }
-// can the wide kernel take this solve?  (whole wavefronts of four trajectories, a horizon with an F, 32-bit time strides;
-// the gain rows travel through the caller's workspace, rows of the INSTANCE's width - dmpc_lqr_workspace_bytes allows for it)
-// the geometric half of wide_ok - shape, batch, horizon and the 32-bit stride bound - shared with dmpc_lqr_solve_path, so that the
-// path a caller is told (and sizes its workspace for) is the path dispatch_lqr takes
-static bool wide_geometry_ok(int T, int B, int nx, int nu) {
-  const bool exact = wide_shape(nx, nu);
-  const bool padded = wide_container_shape(nx, nu) && B % 4 == 0 && !knob_on<Knob::DMPC_NO_CONTAINER>();
-  return (exact || padded) && !knob_on<Knob::DMPC_NO_WIDE>() && B >= 4 && T >= 2 &&
-         (size_t)B * (nx + nu) * (nx + nu) * 4 < ((size_t)1 << 31);
-}
-static bool wide_ok(int mode, int nx, int nu, const LqrArgs &a) {
-  // (the generated streams' own argument forms - c in two arrays, saved gains, x_init = 0 - are not its business)
-  const bool plain = a.c_u == nullptr && a.Ks_in == nullptr && a.Vv_in == nullptr && a.Quu_out == nullptr && a.x_init != nullptr;
-  return mode == kSolve && plain && wide_geometry_ok(a.T, a.B, nx, nu) && a.wsK != nullptr;
-}
-static int launch_lqr_wide(int nx, int nu, const LqrArgs &a, hipStream_t stream) {
-  const dim3 grid((a.B + 15) / 16), block(256);
-#define X(NX_, NU_)                                                                                        \
-  if (nx == NX_ && nu == NU_) {                                                                            \
-    constexpr int DB = 2, DF = 2;                                                                          \
-    constexpr size_t lds = LqrWideLayout<NX_, NU_, DB, DF>::lds_bytes();                                   \
-    static_assert(lds <= 160 * 1024, "rings beyond a CU's LDS");                                           \
-    if (lds > 64 * 1024) {                                                                                 \
-      set_max_lds(reinterpret_cast<const void *>(&lqr_wide_kernel<NX_, NU_, DB, DF>), (int)lds);           \
-      set_max_lds(reinterpret_cast<const void *>(&lqr_wide_kernel<NX_, NU_, DB, DF, false, true>), (int)lds); \
-    }                                                                                                      \
-    if (a.mask != nullptr) {                                                                               \
-      DMPC_LAUNCH_GGL((lqr_wide_kernel<NX_, NU_, DB, DF, false, true>), grid, block, lds, stream, a);      \
-    } else {                                                                                               \
-      DMPC_LAUNCH_GGL((lqr_wide_kernel<NX_, NU_, DB, DF>), grid, block, lds, stream, a);                   \
-    }                                                                                                      \
-    return (int)hipGetLastError();                                                                         \
-  }
-  DMPC_LQR_WIDE_SHAPES(X)
-#undef X
-  LqrArgs p = a;
-  p.nx_log = nx;
-  p.nu_log = nu;
-#define X(NX_, NU_)                                                                                        \
-  if (nx <= NX_ && nu <= NU_) {                                                                            \
-    constexpr int DB = 2, DF = 2;                                                                          \
-    constexpr size_t lds = LqrWideLayout<NX_, NU_, DB, DF>::lds_bytes();                                   \
-    if (lds > 64 * 1024)                                                                                   \
-      set_max_lds(reinterpret_cast<const void *>(&lqr_wide_kernel<NX_, NU_, DB, DF, true>), \
-                                (int)lds);                     \
-    if (p.mask != nullptr) {                                                                               \
-      if (lds > 64 * 1024)                                                                                 \
-        set_max_lds(reinterpret_cast<const void *>(&lqr_wide_kernel<NX_, NU_, DB, DF, true, true>), \
-                                  (int)lds);                   \
-      DMPC_LAUNCH_GGL((lqr_wide_kernel<NX_, NU_, DB, DF, true, true>), grid, block, lds, stream, p);       \
-    } else {                                                                                               \
-      DMPC_LAUNCH_GGL((lqr_wide_kernel<NX_, NU_, DB, DF, true>), grid, block, lds, stream, p);             \
-    }                                                                                                      \
-    return (int)hipGetLastError();                                                                         \
-  }
+// The wide kernel's launcher where it can take a solve of this size, else nullptr: whole wavefronts of four trajectories (a
+// padded shape: nothing but), a horizon with an F, 32-bit time strides.  Its gain rows travel through the caller's workspace,
+// rows of the INSTANCE's width - dmpc_lqr_workspace_bytes allows for it.
+static LqrLauncher wide_launcher(int T, int B, int nx, int nu) {
+  if (knob_on<Knob::DMPC_NO_WIDE>() || !fills_a_wave(T, B) || (size_t)B * (nx + nu) * (nx + nu) * 4 >= ((size_t)1 << 31))
+    return nullptr;
+  if (const LqrLauncher exact = wide_exact_launcher(nx, nu)) return exact;
+  if (!wide_container_shape(nx, nu) || !whole_waves(B) || knob_on<Knob::DMPC_NO_CONTAINER>()) return nullptr;
+#define X(NX_, NU_) \
+  if (nx <= NX_ && nu <= NU_) return launch_wide<NX_, NU_, true>;
   DMPC_LQR_WIDE_CONTAINERS(X)
 #undef X
-  return DMPC_E_UNSUPPORTED;
+  return nullptr;
 }
+constexpr size_t kWideContainerGainFloats = 8 * 25;   // gain rows of a wide container, per trajectory-step: at most 8 rows of 25
 
 static bool has_container(int nx, int nu) {
 #define X(NX_, NU_) \
@@ -371,34 +369,6 @@ static bool has_container(int nx, int nu) {
   DMPC_LQR_WAVE_CONTAINERS(X)
 #undef X
   return false;
-}
-
-// a wider problem (up to 32 states, 8 controls) inside a wavefront-per-trajectory instance: sweep on the matrix cores
-// (lqr_wave_mfma_backward<..., PAD>), gains through HBM, then the forward-only container kernel
-template <int NX, int NU>
-static int launch_lqr_wave_container(int mode, int nx, int nu, const LqrArgs &a0, hipStream_t stream) {
-  LqrArgs a = a0;
-  a.nx_log = nx;
-  a.nu_log = nu;
-  const bool masked = a.mask != nullptr;
-  if (mode != kForwardOnly) {
-    if (a.Ks == nullptr) { a.Ks = a.wsK; a.ks = a.wsk; }
-    if (a.Ks == nullptr) return DMPC_E_WORKSPACE;
-    if (!knob_on<Knob::DMPC_NO_WAVE_MFMA>()) {   // a size that IS one of the instances: the exact kernel (rollout in the same launch)
-      const int rx = launch_lqr_wave_mfma_backward(nx, nu, masked, mode == kSolve, a, stream);
-      if (rx != DMPC_E_UNSUPPORTED) return rx;
-    }
-    const int rc = launch_lqr_wave_container_sweep(NX, NU, masked, a, stream);
-    if (rc != 0 || mode == kBackwardOnly) return rc;
-  }
-  {
-    const int rc = launch_lqr_staged_forward(nx, nu, a, stream);   // (the rows through an LDS ring: lqr_staged_forward.hpp)
-    if (rc != DMPC_E_UNSUPPORTED) return rc;
-  }
-  const dim3 grid((a.B + 3) / 4), block(256);
-  if (masked) DMPC_LAUNCH_GGL((lqr_kernel<NX, NU, 64, true, kForwardOnly, false, true>), grid, block, 0, stream, a);
-  else DMPC_LAUNCH_GGL((lqr_kernel<NX, NU, 64, false, kForwardOnly, false, true>), grid, block, 0, stream, a);
-  return (int)hipGetLastError();
 }
 
 static int lqr_family(int nx, int nu) {
@@ -414,66 +384,76 @@ static int lqr_family(int nx, int nu) {
   return DMPC_E_UNSUPPORTED;
 }
 
-// a problem without a specialisation of its own, in the smallest container that holds it
+// a wider problem (up to 32 states, 8 controls) inside the wavefront-per-trajectory instance (NX, NU): sweep on the matrix cores,
+// gains through HBM, then the rollout - staged through LDS where that applies, else the forward-only container kernel
 template <int NX, int NU>
-static int launch_lqr_container(int mode, int nx, int nu, const LqrArgs &a0, hipStream_t stream) {
-  constexpr int GPB = 16;
-  LqrArgs a = a0;
-  a.nx_log = nx;
-  a.nu_log = nu;
-  const dim3 grid((a.B + GPB - 1) / GPB), block(256);
-  const bool masked = a.mask != nullptr;
-  const size_t lds_gain = (size_t)GPB * a.T * NU * (NX + 1) * sizeof(float);
-#define DMPC_LAUNCH(MASKED, MODE, KLDS, SHMEM) \
-  DMPC_LAUNCH_GGL((lqr_kernel<NX, NU, 16, MASKED, MODE, KLDS, true>), grid, block, SHMEM, stream, a)
-  if (mode == kSolve) {
-    if (lds_gain <= kGainLdsBudget) {
-      if (masked) DMPC_LAUNCH(true, kSolve, true, lds_gain);
-      else DMPC_LAUNCH(false, kSolve, true, lds_gain);
-    } else {
-      if (a.Ks == nullptr) { a.Ks = a.wsK; a.ks = a.wsk; }
-      if (a.Ks == nullptr) return DMPC_E_WORKSPACE;
-      if (masked) DMPC_LAUNCH(true, kSolve, false, 0);
-      else DMPC_LAUNCH(false, kSolve, false, 0);
-    }
-  } else if (mode == kBackwardOnly) {
-    if (masked) DMPC_LAUNCH(true, kBackwardOnly, false, 0);
-    else DMPC_LAUNCH(false, kBackwardOnly, false, 0);
-  } else {
-    if (masked) DMPC_LAUNCH(true, kForwardOnly, false, 0);
-    else DMPC_LAUNCH(false, kForwardOnly, false, 0);
-  }
-#undef DMPC_LAUNCH
-  return (int)hipGetLastError();
+static LqrRoute route_wave_container(const LqrCall &q) {
+  const bool masked = q.form == LqrForm::kMasked;
+  LqrLauncher forward = lqr_staged_forward_launcher(q.T, q.nx, q.nu, masked);
+  if (forward == nullptr) forward = launch_group<NX, NU, 64, kForwardOnly, false, true>;
+  if (q.mode == kForwardOnly) return {DMPC_LQR_PATH_CONTAINER, forward};
+  if (!gains_have_a_place(q)) return {DMPC_E_WORKSPACE};
+  // a size that IS one of the instances: the exact kernel (rollout in the same launch)
+  if (const LqrLauncher exact = lqr_wave_exact_launcher(q.nx, q.nu, masked, q.mode == kSolve))
+    return {DMPC_LQR_PATH_CONTAINER, exact};
+  return {DMPC_LQR_PATH_CONTAINER, lqr_wave_padded_sweep_launcher(q.nx, q.nu, masked), q.mode == kSolve ? forward : nullptr};
 }
 
-static int dispatch_lqr(int mode, int nx, int nu, const LqrArgs &a, hipStream_t stream) {
-  if (wide_ok(mode, nx, nu, a)) return launch_lqr_wide(nx, nu, a, stream);
+static LqrRoute lqr_route(const LqrCall &q) {
+  const int nx = q.nx, nu = q.nu;
+  const bool plain_or_masked = q.form == LqrForm::kPlain || q.form == LqrForm::kMasked;
+  if (q.mode == kSolve && plain_or_masked && q.ws) {
+    if (const LqrLauncher wide = wide_launcher(q.T, q.B, nx, nu)) return {DMPC_LQR_PATH_WIDE, wide};
+  }
 #define X(NX_, NU_, L_) \
-  if (nx == NX_ && nu == NU_) return launch_lqr<NX_, NU_, L_>(mode, a, stream);
+  if (nx == NX_ && nu == NU_) return route_exact<NX_, NU_, L_>(q);
   DMPC_LQR_SHAPES(X)
 #undef X
-  // (the generated streams' own argument forms - lqr_second_solve - stop here: nothing else reads them)
-  if (a.c_u != nullptr || a.Ks_in != nullptr || a.Vv_in != nullptr || a.Quu_out != nullptr ||
-      (a.x_init == nullptr && a.x != nullptr))
-    return DMPC_E_UNSUPPORTED;
+  if (!plain_or_masked) return {DMPC_E_UNSUPPORTED};   // (nothing else reads the generated streams' own argument forms)
   const int family = lqr_family(nx, nu);
+  // a problem without a specialisation of its own, in the smallest container that holds it
   if (family == DMPC_LQR_FAMILY_CONTAINER && !knob_on<Knob::DMPC_NO_CONTAINER>()) {
 #define X(NX_, NU_) \
-  if (nx <= NX_ && nu <= NU_) return launch_lqr_container<NX_, NU_>(mode, nx, nu, a, stream);
+  if (nx <= NX_ && nu <= NU_) return route_group<NX_, NU_, 16, true>(q, DMPC_LQR_PATH_CONTAINER);
     DMPC_LQR_CONTAINERS(X)
 #undef X
 #define X(NX_, NU_) \
-  if (nx <= NX_ && nu <= NU_) return launch_lqr_wave_container<NX_, NU_>(mode, nx, nu, a, stream);
+  if (nx <= NX_ && nu <= NU_) return route_wave_container<NX_, NU_>(q);
     DMPC_LQR_WAVE_CONTAINERS(X)
 #undef X
   }
-  if (family == DMPC_LQR_FAMILY_GENERIC || family == DMPC_LQR_FAMILY_CONTAINER) {
-    const int rc = launch_lqr_generic(mode, nx, nu, a, stream);
-    if (rc != DMPC_E_UNSUPPORTED) return rc;      // (its matrices did not fit in LDS: the tiled kernel takes any size)
-  }
-  if (nx >= 1 && nu >= 1) return launch_lqr_tiled(mode, nx, nu, a, a.tiled_scratch, stream);
-  return DMPC_E_UNSUPPORTED;
+  // (the generic kernel's matrices fit LDS at every size of these two families: lqr_family says so for GENERIC, a container's
+  // size is below it - the tiled kernel is for the rest)
+  if (family == DMPC_LQR_FAMILY_GENERIC || family == DMPC_LQR_FAMILY_CONTAINER)
+    return {DMPC_LQR_PATH_GENERIC,
+            by_mode(q.mode, launch_generic<kSolve>, launch_generic<kBackwardOnly>, launch_generic<kForwardOnly>)};
+  if (family != DMPC_LQR_FAMILY_TILED) return {DMPC_E_UNSUPPORTED};
+  if (q.mode != kForwardOnly && !(q.scratch && gains_have_a_place(q))) return {DMPC_E_WORKSPACE};   // the sweep's matrices live there
+  return {DMPC_LQR_PATH_TILED, by_mode(q.mode, launch_tiled<kSolve>, launch_tiled<kBackwardOnly>, launch_tiled<kForwardOnly>)};
+}
+
+// (writes the problem's dimensions into the entry point's own `a`: the containers read them, the other kernels ignore them)
+static int dispatch_lqr(int mode, LqrForm form, int nx, int nu, LqrArgs &a, hipStream_t stream) {
+  const LqrRoute r = lqr_route({mode, form, a.T, a.B, nx, nu, a.Ks != nullptr, a.wsK != nullptr, a.tiled_scratch != nullptr,
+                                (reinterpret_cast<uintptr_t>(a.mask) & 3u) == 0});
+  if (r.path < 0) return r.path;   // (nothing launched)
+  a.nx_log = nx;
+  a.nu_log = nu;
+  const int rc = r.launch(a, stream);
+  return rc != 0 || r.then == nullptr ? rc : r.then(a, stream);
+}
+
+// the arguments every form of a call has
+static LqrArgs lqr_args(int T, int B, const float *C, const float *c, const float *F, const float *f, const float *x_init,
+                        float *x, float *u, int32_t *info) {
+  LqrArgs a{};
+  a.T = T; a.B = B;
+  a.C = C; a.c = c; a.F = F; a.f = f; a.x_init = x_init;
+  a.x = x; a.u = u; a.info = info;
+  return a;
+}
+static void set_saved_gains(LqrArgs &a, const float *Ks, const float *Quu, const float *Qxu) {
+  a.Ks_in = Ks; a.Quu_in = Quu; a.Qxu_in = Qxu;
 }
 
 // DiffLqr.backward's second solve (differentiable_lqr.py:108-114) without a concatenated copy of its inputs: c = [cx; cu]
@@ -482,15 +462,10 @@ static int dispatch_lqr(int mode, int nx, int nu, const LqrArgs &a, hipStream_t 
 int lqr_second_solve(int T, int B, int nx, int nu, const float *C, const float *cx, const float *cu, const float *F,
                      const float *Ks, const float *Quu, const float *Qxu, float *x_out, float *u_out, int32_t *info,
                      hipStream_t stream) {
-  LqrArgs a{T, B, C, cx, F, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, x_out, u_out, info};
+  LqrArgs a = lqr_args(T, B, C, cx, F, nullptr, nullptr, x_out, u_out, info);
   a.c_u = cu;
-  if (Ks != nullptr) {
-    if (B % 4 != 0) return DMPC_E_UNSUPPORTED;
-    a.Ks_in = Ks;
-    a.Quu_in = Quu;
-    a.Qxu_in = Qxu;
-  }
-  return dispatch_lqr(kSolve, nx, nu, a, stream);
+  if (Ks != nullptr) set_saved_gains(a, Ks, Quu, Qxu);
+  return dispatch_lqr(kSolve, Ks != nullptr ? LqrForm::kSaved : LqrForm::kSplitC, nx, nu, a, stream);
 }
 
 // DiffLqr.backward (differentiable_lqr.py:78-142) in ONE launch that reads neither C nor c: the affine re-solve from the
@@ -500,12 +475,9 @@ int lqr_second_solve(int T, int B, int nx, int nu, const float *C, const float *
 int lqr_adjoint(int T, int B, int nx, int nu, const float *F, const float *grad_x, const float *grad_u, const float *Ks,
                 const float *Quu, const float *Qxu, const float *Vv, const float *x, const float *u, int strict_math,
                 float *d_x_init, float *dC, float *dc, float *dF, float *df, int32_t *info, hipStream_t stream) {
-  if (B % 4 != 0) return DMPC_E_UNSUPPORTED;
-  LqrArgs a{T, B, nullptr, grad_x, F, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, info};
+  LqrArgs a = lqr_args(T, B, nullptr, grad_x, F, nullptr, nullptr, nullptr, nullptr, info);
   a.c_u = grad_u;
-  a.Ks_in = Ks;
-  a.Quu_in = Quu;
-  a.Qxu_in = Qxu;
+  set_saved_gains(a, Ks, Quu, Qxu);
   a.Vv_in = Vv;
   a.tau_x = x;
   a.tau_u = u;
@@ -513,12 +485,22 @@ int lqr_adjoint(int T, int B, int nx, int nu, const float *F, const float *grad_
   a.w_a = 0.5f;
   a.w_b = strict_math ? 0.5f : 1.0f;
   a.df_shift = strict_math ? 1 : 0;
-  return dispatch_lqr(kSolve, nx, nu, a, stream);
+  return dispatch_lqr(kSolve, LqrForm::kAdjoint, nx, nu, a, stream);
 }
 
 }  // namespace dmpc
 
 using namespace dmpc;
+
+// what a caller is told: the route of a solve of this form that brings the workspace (the queries have no pointers to go by)
+static LqrRoute told_route(int T, int B, int nx, int nu, LqrForm form, bool gains) {
+  return lqr_route({kSolve, form, T, B, nx, nu, gains, true, true, true});
+}
+// gain rows in the workspace: [T,B,nu,nx] + [T,B,nu], or - the generated stream at long horizons - rows of 12 floats
+// [K_m | 0 | k_m | pad], or rows of nx + nu + 1 floats (the LDS-DMA kernel's workspace form)
+static size_t gain_ws_bytes(int T, int B, int nx, int nu) {
+  return (size_t)T * B * nu * (nx + nu + 1 > 12 ? nx + nu + 1 : 12) * sizeof(float);
+}
 
 extern "C" {
 
@@ -528,36 +510,19 @@ int dmpc_lqr_kernel_family(int nx, int nu) { return lqr_family(nx, nu); }
 
 int dmpc_lqr_solve_path(int T, int B, int nx, int nu) {
   if (T <= 0 || B <= 0) return DMPC_E_BADARG;
-  if (wide_shape(nx, nu) && wide_geometry_ok(T, B, nx, nu)) return DMPC_LQR_PATH_WIDE;   // lqr_wide_kernel (given the workspace)
-#define X(NX_, NU_, L_) \
-  if (nx == NX_ && nu == NU_) return solve_path<NX_, NU_, L_>(T, B);
-  DMPC_LQR_SHAPES(X)
-#undef X
-  if (wide_container_shape(nx, nu) && wide_geometry_ok(T, B, nx, nu)) return DMPC_LQR_PATH_WIDE;
-  const int family = lqr_family(nx, nu);
-  if (family == DMPC_LQR_FAMILY_CONTAINER && !knob_on<Knob::DMPC_NO_CONTAINER>()) return DMPC_LQR_PATH_CONTAINER;
-  if (family == DMPC_LQR_FAMILY_TILED) return DMPC_LQR_PATH_TILED;
-  if (family == DMPC_LQR_FAMILY_GENERIC || family == DMPC_LQR_FAMILY_CONTAINER) return DMPC_LQR_PATH_GENERIC;
-  return DMPC_E_UNSUPPORTED;
+  return told_route(T, B, nx, nu, LqrForm::kPlain, false).path;   // a plain solve that takes no gains
 }
 
 int dmpc_lqr_saving_available(int T, int B, int nx, int nu) {
-  if (T <= 1 || B <= 0 || B % 4 != 0) return 0;
-#define X(NX_, NU_, L_) \
-  if (nx == NX_ && nu == NU_) return saving_available<NX_, NU_, L_>(T, B);
-  DMPC_LQR_SHAPES(X)
-#undef X
-  return 0;
+  return T > 0 && B > 0 && told_route(T, B, nx, nu, LqrForm::kSaving, true).path >= 0;
 }
 
 size_t dmpc_lqr_workspace_bytes(int T, int B, int nx, int nu) {
   if (T <= 0 || B <= 0 || nx <= 0 || nu <= 0) return 0;
-  // gains [T,B,nu,nx] + [T,B,nu], or - the generated stream at long horizons - rows of 12 floats [K_m | 0 | k_m | pad];
-  // only touched when they do not fit in LDS (long horizons) or by the generic kernel
-  // (rows of nx + nu + 1 floats for the LDS-DMA HIP kernel's workspace form)
-  size_t bytes = (size_t)T * B * nu * (nx + nu + 1 > 12 ? nx + nu + 1 : 12) * sizeof(float);
-  // (a shape padded inside an instance of the wide row kernel: gain rows of the INSTANCE's width - at most 8 rows of 25)
-  if (wide_container_shape(nx, nu)) bytes = (size_t)T * B * 8 * 25 * sizeof(float);
+  // only touched when the gains do not fit in LDS (long horizons) or by the generic kernel
+  size_t bytes = gain_ws_bytes(T, B, nx, nu);
+  // (a shape padded inside an instance of the wide row kernel: gain rows of the INSTANCE's width)
+  if (wide_container_shape(nx, nu)) bytes = (size_t)T * B * kWideContainerGainFloats * sizeof(float);
   // the shapes beyond a wavefront's 64 columns (the tiled family) keep the matrices of every trajectory behind the gains
   if (lqr_family(nx, nu) == DMPC_LQR_FAMILY_TILED)
     bytes = round_up(bytes, 256) + (size_t)B * tiled_scratch_floats(nx, nu) * sizeof(float);
@@ -566,8 +531,7 @@ size_t dmpc_lqr_workspace_bytes(int T, int B, int nx, int nu) {
 
 static float *tiled_scratch_of(void *ws, int T, int B, int nx, int nu) {
   if (ws == nullptr || lqr_family(nx, nu) != DMPC_LQR_FAMILY_TILED) return nullptr;
-  return reinterpret_cast<float *>(static_cast<char *>(ws) +
-                                   round_up((size_t)T * B * nu * (nx + nu + 1 > 12 ? nx + nu + 1 : 12) * sizeof(float), 256));
+  return reinterpret_cast<float *>(static_cast<char *>(ws) + round_up(gain_ws_bytes(T, B, nx, nu), 256));
 }
 
 int dmpc_lqr_solve(int T, int B, int nx, int nu, const float *C, const float *c, const float *F,
@@ -578,14 +542,16 @@ int dmpc_lqr_solve(int T, int B, int nx, int nu, const float *C, const float *c,
   if (!C || !c || !x_init || !x_out || !u_out || (T > 1 && !F)) return DMPC_E_BADARG;
   if ((Ks_out == nullptr) != (ks_out == nullptr)) return DMPC_E_BADARG;
   if (!aligned16(C) || !aligned16(c) || !aligned16(F) || !aligned16(f)) return DMPC_E_BADARG;
-  LqrArgs a{T, B, C, c, F, f, x_init, u_zero_mask, Ks_out, ks_out, nullptr, nullptr, x_out, u_out, info};
+  LqrArgs a = lqr_args(T, B, C, c, F, f, x_init, x_out, u_out, info);
+  a.mask = u_zero_mask;
+  a.Ks = Ks_out; a.ks = ks_out;
   if (ws != nullptr) {
     if (ws_bytes < dmpc_lqr_workspace_bytes(T, B, nx, nu)) return DMPC_E_WORKSPACE;
     a.wsK = static_cast<float *>(ws);
     a.wsk = a.wsK + (size_t)T * B * nu * nx;
     a.tiled_scratch = tiled_scratch_of(ws, T, B, nx, nu);
   }
-  return dispatch_lqr(kSolve, nx, nu, a, static_cast<hipStream_t>(stream));
+  return dispatch_lqr(kSolve, u_zero_mask ? LqrForm::kMasked : LqrForm::kPlain, nx, nu, a, static_cast<hipStream_t>(stream));
 }
 
 int dmpc_lqr_solve_saving(int T, int B, int nx, int nu, const float *C, const float *c, const float *F,
@@ -595,13 +561,11 @@ int dmpc_lqr_solve_saving(int T, int B, int nx, int nu, const float *C, const fl
   if (!C || !c || !F || !x_init || !x_out || !u_out || !Ks_out || !ks_out || !Quu_out || !Qxu_out || !Vv_out)
     return DMPC_E_BADARG;
   if (!aligned16(C) || !aligned16(c) || !aligned16(F) || !aligned16(f) || !aligned16(Quu_out)) return DMPC_E_BADARG;
-  if (!dmpc_lqr_saving_available(T, B, nx, nu)) return DMPC_E_UNSUPPORTED;   // the stash form of the generated stream only
-  LqrArgs a{T, B, C, c, F, f, x_init, nullptr, Ks_out, ks_out, nullptr, nullptr, x_out, u_out, info};
-  a.Quu_out = Quu_out;
-  a.Qxu_out = Qxu_out;
-  a.Vv_out = Vv_out;
+  LqrArgs a = lqr_args(T, B, C, c, F, f, x_init, x_out, u_out, info);
+  a.Ks = Ks_out; a.ks = ks_out;
+  a.Quu_out = Quu_out; a.Qxu_out = Qxu_out; a.Vv_out = Vv_out;
   a.info_store = true;
-  return dispatch_lqr(kSolve, nx, nu, a, static_cast<hipStream_t>(stream));
+  return dispatch_lqr(kSolve, LqrForm::kSaving, nx, nu, a, static_cast<hipStream_t>(stream));   // (the stash form of the stream only)
 }
 
 int dmpc_lqr_saved_solve(int T, int B, int nx, int nu, const float *c, const float *F, const float *Ks,
@@ -610,12 +574,9 @@ int dmpc_lqr_saved_solve(int T, int B, int nx, int nu, const float *c, const flo
   if (T <= 1 || B <= 0 || nx <= 0 || nu <= 0) return DMPC_E_BADARG;
   if (!c || !F || !Ks || !Quu || !Qxu || !x_init || !x_out || !u_out) return DMPC_E_BADARG;
   if (!aligned16(c) || !aligned16(F) || !aligned16(Ks) || !aligned16(Quu) || !aligned16(Qxu)) return DMPC_E_BADARG;
-  if (dmpc_lqr_solve_path(T, B, nx, nu) != DMPC_LQR_PATH_ASM_STASH || B % 4 != 0) return DMPC_E_UNSUPPORTED;
-  LqrArgs a{T, B, nullptr, c, F, nullptr, x_init, nullptr, nullptr, nullptr, nullptr, nullptr, x_out, u_out, info};
-  a.Ks_in = Ks;
-  a.Quu_in = Quu;
-  a.Qxu_in = Qxu;
-  return dispatch_lqr(kSolve, nx, nu, a, static_cast<hipStream_t>(stream));
+  LqrArgs a = lqr_args(T, B, nullptr, c, F, nullptr, x_init, x_out, u_out, info);
+  set_saved_gains(a, Ks, Quu, Qxu);
+  return dispatch_lqr(kSolve, LqrForm::kSaved, nx, nu, a, static_cast<hipStream_t>(stream));
 }
 
 int dmpc_lqr_backward_sweep_ws(int T, int B, int nx, int nu, const float *C, const float *c, const float *F,
@@ -624,12 +585,14 @@ int dmpc_lqr_backward_sweep_ws(int T, int B, int nx, int nu, const float *C, con
   if (T <= 0 || B <= 0 || nx <= 0 || nu <= 0) return DMPC_E_BADARG;
   if (!C || !c || !Ks_out || !ks_out || (T > 1 && !F)) return DMPC_E_BADARG;
   if (!aligned16(C) || !aligned16(c) || !aligned16(F) || !aligned16(f)) return DMPC_E_BADARG;
-  LqrArgs a{T, B, C, c, F, f, nullptr, u_zero_mask, Ks_out, ks_out, nullptr, nullptr, nullptr, nullptr, info};
+  LqrArgs a = lqr_args(T, B, C, c, F, f, nullptr, nullptr, nullptr, info);
+  a.mask = u_zero_mask;
+  a.Ks = Ks_out; a.ks = ks_out;
   if (ws != nullptr) {
     if (ws_bytes < dmpc_lqr_workspace_bytes(T, B, nx, nu)) return DMPC_E_WORKSPACE;
     a.tiled_scratch = tiled_scratch_of(ws, T, B, nx, nu);
   }
-  return dispatch_lqr(kBackwardOnly, nx, nu, a, static_cast<hipStream_t>(stream));
+  return dispatch_lqr(kBackwardOnly, u_zero_mask ? LqrForm::kMasked : LqrForm::kPlain, nx, nu, a, static_cast<hipStream_t>(stream));
 }
 
 int dmpc_lqr_backward_sweep(int T, int B, int nx, int nu, const float *C, const float *c, const float *F,
@@ -644,9 +607,10 @@ int dmpc_lqr_forward_sweep(int T, int B, int nx, int nu, const float *Ks, const 
   if (T <= 0 || B <= 0 || nx <= 0 || nu <= 0) return DMPC_E_BADARG;
   if (!Ks || !ks || !x_init || !x_out || !u_out || (T > 1 && !F)) return DMPC_E_BADARG;
   if (!aligned16(F) || !aligned16(f)) return DMPC_E_BADARG;
-  LqrArgs a{T, B, nullptr, nullptr, F, f, x_init, u_zero_mask, const_cast<float *>(Ks),
-            const_cast<float *>(ks), nullptr, nullptr, x_out, u_out, info};
-  return dispatch_lqr(kForwardOnly, nx, nu, a, static_cast<hipStream_t>(stream));
+  LqrArgs a = lqr_args(T, B, nullptr, nullptr, F, f, x_init, x_out, u_out, info);
+  a.mask = u_zero_mask;
+  a.Ks = const_cast<float *>(Ks); a.ks = const_cast<float *>(ks);
+  return dispatch_lqr(kForwardOnly, u_zero_mask ? LqrForm::kMasked : LqrForm::kPlain, nx, nu, a, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
