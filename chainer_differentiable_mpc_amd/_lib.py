@@ -65,6 +65,9 @@ SIGNATURES = {
     "dmpc_mlp_dx_supported": (_c_i, [_c_i] * 4),
     "dmpc_mlp_rollout_linearize": (_c_i, [_c_i] * 7 + [_c_f] * 10),
     "dmpc_mpc_forward_rec_mlp": (_c_i, [_c_i] * 7 + [_c_f] * 12 + [ctypes.c_float, _c_i] + [_c_f] * 10),
+    "dmpc_mlp_param_grad_partials": (_c_i, [_c_i]),
+    "dmpc_mlp_param_grad_workspace_bytes": (_c_sz, [_c_i] * 4),
+    "dmpc_mlp_param_grad": (_c_i, [_c_i] * 7 + [_c_f] * 13 + [_c_f, _c_sz, _c_f]),
     "dmpc_mpc_step_backward": (_c_i, [_c_i] * 4 + [_c_f] * 9 + [_c_f] * 7 + [_c_f, _c_f, ctypes.c_float]
                                + [_c_f, _c_sz, _c_f, _c_f]),
     "dmpc_lin_rollout": (_c_i, [_c_i] * 4 + [_c_f] * 6),

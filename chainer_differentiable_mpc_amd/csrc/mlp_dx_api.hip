@@ -1,6 +1,7 @@
 // mlp_dx_api.hip - C-ABI entry points of the learned one-hidden-layer dynamics model (include/dmpc.h section E,
-// "MlpDx"): the nominal rollout with its analytic linearisation, and MPCstep.forward_rec with the network as the true
-// dynamics.  Every argument and size check comes before the first HIP call.
+// "MlpDx"): the nominal rollout with its analytic linearisation, MPCstep.forward_rec with the network as the true
+// dynamics, and the gradient of the linearisation's f with respect to the weights.  Every argument and size check comes
+// before the first HIP call.
 #include <hip/hip_runtime.h>
 
 #include "../../include/dmpc.h"
@@ -58,6 +59,43 @@ int dmpc_mpc_forward_rec_mlp(int T, int B, int nx, int nu, int n_hidden, int act
   const MlpModel m{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2};
   DMPC_LAUNCH_GGL(mpc_forward_rec_mlp_kernel, dim3((B + kMlpWaves - 1) / kMlpWaves), dim3(64 * kMlpWaves),
                   mlp_lds_bytes(nx, nu, n_hidden), static_cast<hipStream_t>(stream_), fa, m);
+  return (int)hipGetLastError();
+}
+
+int dmpc_mlp_param_grad_partials(int B) { return B > 0 ? mlp_grad_partials(B) : 0; }
+
+size_t dmpc_mlp_param_grad_workspace_bytes(int B, int nx, int nu, int n_hidden) {
+  if (B <= 0 || mlp_check(nx, nu, n_hidden, 0) != 0) return 0;
+  return (size_t)mlp_grad_partials(B) * mlp_grad_partial_floats(nx, nu, n_hidden) * sizeof(float);
+}
+
+int dmpc_mlp_param_grad(int T, int B, int nx, int nu, int n_hidden, int act, int residual, const float *W1,
+                        const float *b1, const float *W2, const float *b2, const float *x, const float *u,
+                        const float *grad_f, float *dW1, float *db1, float *dW2, float *db2, float *d_x_init, float *d_u,
+                        void *ws, size_t ws_bytes, dmpc_stream_t stream_) {
+  if (T <= 0 || B <= 0 || nx <= 0 || nu <= 0) return DMPC_E_BADARG;
+  if (!W1 || !b1 || !W2 || !b2 || !x || !u || !dW1 || !db1 || !dW2 || !db2) return DMPC_E_BADARG;
+  if (T > 1 && !grad_f) return DMPC_E_BADARG;
+  const int rc = mlp_check(nx, nu, n_hidden, act);
+  if (rc != 0) return rc;
+  if ((size_t)T * B * nx * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;   // (the rollout's own limit)
+  if (T > 1 && (ws == nullptr || ws_bytes < dmpc_mlp_param_grad_workspace_bytes(B, nx, nu, n_hidden))) return DMPC_E_WORKSPACE;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int G = T > 1 ? mlp_grad_partials(B) : 0;
+  if (T == 1) {            // no dynamics step: every gradient is zero
+    hipError_t e = hipSuccess;
+    if (d_x_init != nullptr) e = hipMemsetAsync(d_x_init, 0, (size_t)B * nx * sizeof(float), stream);
+    if (e == hipSuccess && d_u != nullptr) e = hipMemsetAsync(d_u, 0, (size_t)B * nu * sizeof(float), stream);
+    if (e != hipSuccess) return (int)e;
+  } else {
+    MlpGradArgs ga{T, B, G, MlpModel{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2}, x, u, grad_f,
+                   static_cast<float *>(ws), d_x_init, d_u};
+    DMPC_LAUNCH_GGL(mlp_param_grad_kernel, dim3((G + kMlpWaves - 1) / kMlpWaves), dim3(64 * kMlpWaves),
+                    mlp_lds_bytes(nx, nu, n_hidden), stream, ga);
+  }
+  MlpGradReduceArgs rd{G, nx, nu, n_hidden, static_cast<const float *>(ws), dW1, db1, dW2, db2};
+  DMPC_LAUNCH_GGL(mlp_param_grad_reduce_kernel, dim3((mlp_grad_partial_floats(nx, nu, n_hidden) + 255) / 256), dim3(256), 0,
+                  stream, rd);
   return (int)hipGetLastError();
 }
 

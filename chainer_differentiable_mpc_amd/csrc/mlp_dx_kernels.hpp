@@ -8,6 +8,8 @@
 //   mpc_forward_rec_mlp_kernel     MPCstep.forward_rec (mpc/mpc_step.py:175-286) with the network as the TRUE dynamics:
 //                                  the clamped closed-loop rollout and per-trajectory line search of
 //                                  mpc_generic_forward_kernel, the dynamics evaluated in place of F tau + f.
+//   mlp_param_grad_kernel,         the gradient of a loss of the rollout's f with respect to W1, b1, W2, b2: per-wavefront
+//   mlp_param_grad_reduce_kernel   sums in registers, then a fixed-order reduction of the partials (at the end of this file).
 //
 // Layout.  Runtime dimensions (nx <= 16, nu <= 8, 1 <= H <= 256), ONE wavefront per trajectory, four per workgroup.
 // The weights are staged into LDS once per workgroup and shared by its wavefronts:
@@ -283,6 +285,137 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(con
     a.n_ls[b] = n_pass;
     if (a.info != nullptr && info_bits != 0) atomicOr(&a.info[b], info_bits);
   }
+}
+
+// The gradient of L(f) with respect to W1, b1, W2, b2 for f_t = next(x_t, u_t) - F_t [x_t;u_t] along the rolled states,
+// F_t a CONSTANT with the value of the live Jacobian (MlpDx.linearize; mpc/approximate.py:77-119).  With z_t = [x_t;u_t],
+// a_t = tanh(W1 z_t + b1), g_t = dL/df_t, lam_{T-1} = 0, for t = T-2 .. 0:
+//     r     = g_t + lam_{t+1}
+//     delta = (1 - a_t^2) * (W2^T r)
+//     dW2 += r a_t^T ;  db2 += r ;  dW1 += delta z_t^T ;  db1 += delta
+//     e     = (1 - a_t^2) * (W2^T lam_{t+1}) ;  du_t = W1[:, nx:]^T e ;  lam_t = W1[:, :nx]^T e (+ lam_{t+1} when residual)
+// Every term of lam_t carries a factor lam_{t+1}, and lam_{T-1} = 0: lam_t = 0, e = 0 and du_t = 0 for every t, as exact
+// zeros in any arithmetic - next's derivative through z_t and F_t's cancel at every step, nothing is left to carry.
+// So r = g_t, the lines of e, du and lam are not evaluated, and d_x_init, d_u are stored as the zeros they are.
+//
+// One wavefront per trajectory as above; wavefront w of G serves trajectories w, w + G, ... in ascending order, t
+// descending, and keeps the sums for ITS hidden units (lane, lane + 64, ...) in registers - rows of dW1, columns of dW2,
+// db1; lanes < nx keep db2 - every array indexed by unrolled loops with wave-uniform guards, never by a runtime value.
+// It stores one partial [dW1 | db1 | dW2 | db2], laid out as the parameters are, at part + w * P.
+// mlp_param_grad_reduce_kernel adds the G partials per element in ascending order: no atomics, and a result that depends
+// on (T, B, nx, nu, H) and the data alone.
+constexpr int kMlpGradCap = 512;                             // partials at most: 21.5 MB at the largest model
+__host__ __device__ inline int mlp_grad_partials(int B) { return B < kMlpGradCap ? B : kMlpGradCap; }
+__host__ __device__ inline int mlp_grad_partial_floats(int nx, int nu, int H) { return H * (nx + nu) + H + nx * H + nx; }
+
+struct MlpGradArgs {
+  int T, B, G;
+  MlpModel m;
+  const float *x, *u, *grad_f;   // [T,B,nx] as the rollout stored them, [T,B,nu], [T-1,B,nx]
+  float *part;                   // [G][P]
+  float *d_x_init, *d_u;         // [B,nx], [T,B,nu], each or nullptr
+};
+
+__global__ __launch_bounds__(64 * kMlpWaves) void mlp_param_grad_kernel(const MlpGradArgs a) {
+  extern __shared__ float lds[];
+  const MlpLds L = mlp_stage(a.m, lds);
+  const int lane = threadIdx.x % 64;
+  const int w = blockIdx.x * kMlpWaves + threadIdx.x / 64;
+  if (w >= a.G) return;      // (after the only barrier)
+  const int nx = a.m.nx, nu = a.m.nu, ns = nx + nu, H = a.m.n_hidden;
+  const int n_units = (H + 63) / 64;
+  const int T = a.T;
+  const size_t B = (size_t)a.B;
+  int row[kMlpUnits];
+  bool has[kMlpUnits];
+#pragma unroll
+  for (int k = 0; k < kMlpUnits; ++k) {
+    has[k] = lane + 64 * k < H;
+    row[k] = has[k] ? lane + 64 * k : H - 1;
+  }
+  float dW1[kMlpUnits][kMlpMaxNx + kMlpMaxNu] = {}, dW2[kMlpUnits][kMlpMaxNx] = {}, db1[kMlpUnits] = {}, db2 = 0.f;
+
+  for (size_t b = w; b < B; b += a.G) {
+    if (a.d_x_init != nullptr && lane < nx) a.d_x_init[b * nx + lane] = 0.f;
+    if (a.d_u != nullptr && lane < nu)
+      for (int t = 0; t < T; ++t) a.d_u[((size_t)t * B + b) * nu + lane] = 0.f;
+    for (int t = T - 2; t >= 0; --t) {
+      const size_t tb = (size_t)t * B + b;
+      const float tau = lane < nx ? a.x[tb * nx + lane] : (lane < ns ? a.u[tb * nu + (lane - nx)] : 0.f);
+      const float r = lane < nx ? a.grad_f[tb * nx + lane] : 0.f;
+      float act[kMlpUnits];
+      (void)mlp_next(a.m, L, lane, tau, act);
+      db2 += r;
+      float s[kMlpUnits] = {};                               // W2^T r at this lane's units
+#pragma unroll
+      for (int i = 0; i < kMlpMaxNx; ++i) {
+        if (i < nx) {
+          const float ri = lane_value(r, i);
+#pragma unroll
+          for (int k = 0; k < kMlpUnits; ++k) {
+            if (k < n_units) {
+              const float w2 = L.W2s[i * L.hp + row[k]];
+              s[k] = fmaf(has[k] ? w2 : 0.f, ri, s[k]);
+              dW2[k][i] = fmaf(ri, act[k], dW2[k][i]);
+            }
+          }
+        }
+      }
+      float delta[kMlpUnits];
+#pragma unroll
+      for (int k = 0; k < kMlpUnits; ++k) {
+        delta[k] = fmaf(-act[k], act[k], 1.0f) * s[k];
+        db1[k] += delta[k];
+      }
+#pragma unroll
+      for (int j = 0; j < kMlpMaxNx + kMlpMaxNu; ++j) {
+        if (j < ns) {
+          const float tj = lane_value(tau, j);
+#pragma unroll
+          for (int k = 0; k < kMlpUnits; ++k)
+            if (k < n_units) dW1[k][j] = fmaf(delta[k], tj, dW1[k][j]);
+        }
+      }
+    }
+  }
+
+  float *p = a.part + (size_t)w * mlp_grad_partial_floats(nx, nu, H);
+  float *pb1 = p + H * ns, *pW2 = pb1 + H, *pb2 = pW2 + nx * H;
+#pragma unroll
+  for (int k = 0; k < kMlpUnits; ++k) {
+    const int h = lane + 64 * k;
+    if (h < H) {
+#pragma unroll
+      for (int j = 0; j < kMlpMaxNx + kMlpMaxNu; ++j)
+        if (j < ns) p[h * ns + j] = dW1[k][j];
+      pb1[h] = db1[k];
+#pragma unroll
+      for (int i = 0; i < kMlpMaxNx; ++i)
+        if (i < nx) pW2[i * H + h] = dW2[k][i];
+    }
+  }
+  if (lane < nx) pb2[lane] = db2;
+}
+
+struct MlpGradReduceArgs {
+  int G, nx, nu, n_hidden;
+  const float *part;               // [G][P]
+  float *dW1, *db1, *dW2, *db2;    // [H,ns], [H], [nx,H], [nx]
+};
+
+// one thread per parameter element; G = 0 stores zeros (T = 1: no dynamics step, no partials)
+__global__ __launch_bounds__(256) void mlp_param_grad_reduce_kernel(const MlpGradReduceArgs a) {
+  const int H = a.n_hidden, n1 = H * (a.nx + a.nu), n2 = a.nx * H;
+  const int P = mlp_grad_partial_floats(a.nx, a.nu, H);
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= P) return;
+  float s = 0.f;
+#pragma unroll 8
+  for (int w = 0; w < a.G; ++w) s += a.part[(size_t)w * P + e];
+  if (e < n1) a.dW1[e] = s;
+  else if (e < n1 + H) a.db1[e - n1] = s;
+  else if (e < n1 + H + n2) a.dW2[e - n1 - H] = s;
+  else a.db2[e - n1 - H - n2] = s;
 }
 
 }  // namespace dmpc

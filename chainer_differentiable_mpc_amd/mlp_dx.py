@@ -9,20 +9,25 @@ evaluates the network inside its kernel (`dmpc_mpc_forward_rec_mlp`); the hooks 
 nothing is cached, so an optimiser step in place is seen by the next call.
 
 Learning the weights follows mpc/approximate.py:77-119: the Jacobians F_t are constants of the graph, f_t = next - F_t [x;u]
-stays on it through `next` and the re-rolled states, and `MPCstep.backward`'s df reaches W1, b1, W2, b2."""
+stays on it through `next` and the re-rolled states, and `MPCstep.backward`'s df reaches W1, b1, W2, b2.  By default that
+graph is a live torch rollout; with `device_grad=True` it is one autograd node around the rollout's launch whose backward
+is `dmpc_mlp_param_grad` (one sweep kernel, one fixed-order reduction)."""
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
+from .lqr_recursion import _workspace
 from .util import bmv
 
 ACT_TANH = 0     # the `act` argument of the C ABI
 
 
 class MlpDx(torch.nn.Module):
-    def __init__(self, n_state, n_ctrl, n_hidden, residual=True, seed=None):
+    def __init__(self, n_state, n_ctrl, n_hidden, residual=True, seed=None, device_grad=False):
         super().__init__()
+        self.device_grad = bool(device_grad)
         self.n_state, self.n_ctrl, self.n_hidden = int(n_state), int(n_ctrl), int(n_hidden)
         self.residual = bool(residual)
         ns = self.n_state + self.n_ctrl
@@ -124,7 +129,8 @@ class MlpDx(torch.nn.Module):
     def linearize(self, x, u):
         """F_t = d next / d [x;u], f_t = next - F_t [x_t;u_t] along the trajectory re-rolled from x[0] (the contract of
         `PendulumDx.linearize`).  No gradient wanted: all of it from the kernel.  Otherwise F still comes from the kernel on
-        the GPU, next and the re-rolled states from a live torch rollout."""
+        the GPU, next and the re-rolled states from a live torch rollout - or, with `device_grad`, f too comes from the
+        kernel and its gradient from `dmpc_mlp_param_grad`."""
         T = x.shape[0]
         x0 = x[0]
         if self.fused_ok(x0, u):
@@ -133,6 +139,8 @@ class MlpDx(torch.nn.Module):
         if not self._grad_wanted(x0, u):
             _, F, f = self._rollout_linearize_torch(x0, u, True)
             return F, f
+        if self.device_grad and self._on_device(x0, u):
+            return _DeviceLinearize.apply(self, *self._weights(), x0, u)
         F_dev = None
         if self._on_device(x0, u):
             F_dev = self.rollout_linearize(x0, u)[1]
@@ -149,3 +157,45 @@ class MlpDx(torch.nn.Module):
             _, F, f = self._rollout_linearize_torch(x0.detach(), u.detach(), True)
             return F, f
         return torch.stack(Fs, 0), torch.stack(fs, 0)
+
+
+class _DeviceLinearize(torch.autograd.Function):
+    """(F, f) of `MlpDx.linearize` as ONE node over (W1, b1, W2, b2, x[0], u): forward is the rollout's launch, backward
+    `dmpc_mlp_param_grad`.  F is a constant of the graph.  The weights are saved as autograd saves any input, so one
+    changed in place before the backward is autograd's version error, not a gradient at other weights than the forward's."""
+
+    @staticmethod
+    def forward(ctx, model, W1, b1, W2, b2, x0, u):
+        x, F, f = model.rollout_linearize(x0, u)
+        ctx.model = model
+        ctx.save_for_backward(W1, b1, W2, b2, x, u)
+        ctx.mark_non_differentiable(F)
+        return F, f
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, _grad_F, grad_f):
+        m = ctx.model
+        *weights, x, u = ctx.saved_tensors
+        T, B = u.shape[0], u.shape[1]
+        nx, nu, H = m.n_state, m.n_ctrl, m.n_hidden
+        lib = _lib.load()
+        d = u.device
+        W1, b1, W2, b2 = (_lib.f32c(p.detach(), d) for p in weights)
+        xs, ud, g = _lib.f32c(x, d), _lib.f32c(u.detach(), d), _lib.f32c(grad_f, d)
+        assert list(xs.shape) == [T, B, nx] and list(g.shape) == [max(T - 1, 0), B, nx]
+        f32 = dict(dtype=torch.float32, device=d)
+        dW1, db1, dW2, db2 = (torch.empty(p.shape, **f32) for p in (W1, b1, W2, b2))
+        dx0 = torch.empty((B, nx), **f32) if ctx.needs_input_grad[5] else None
+        du = torch.empty((T, B, nu), **f32) if ctx.needs_input_grad[6] else None
+        nbytes = lib.dmpc_mlp_param_grad_workspace_bytes(B, nx, nu, H)
+        ws = _workspace(nbytes, d)
+        with _lib.guard(d):
+            rc = lib.dmpc_mlp_param_grad(T, B, nx, nu, H, ACT_TANH, int(m.residual), _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2),
+                                         _lib.ptr(b2), _lib.ptr(xs), _lib.ptr(ud), _lib.ptr(g), _lib.ptr(dW1), _lib.ptr(db1),
+                                         _lib.ptr(dW2), _lib.ptr(db2), _lib.ptr(dx0), _lib.ptr(du), _lib.ptr(ws), nbytes,
+                                         _lib.stream_ptr(d))
+        _lib.check(rc, "dmpc_mlp_param_grad")
+        grads = [gr.to(p.dtype) if need else None
+                 for gr, p, need in zip((dW1, db1, dW2, db2), weights, ctx.needs_input_grad[1:5])]
+        return (None, *grads, None if dx0 is None else dx0.to(grad_f.dtype), None if du is None else du.to(u.dtype))

@@ -314,7 +314,18 @@ int dmpc_pendulum_rollout_linearize(int T, int B, const float *x_init, const flo
  *   NULL).  T = 1: x_out = x_init, nothing else is written.
  * dmpc_mpc_forward_rec_mlp: dmpc_mpc_forward_rec (its arguments, outputs, per-trajectory termination, bound snap, test on the
  *   cost difference, cap of 64 passes with DMPC_INFO_LS_ITERCAP, DMPC_INFO_NONFINITE) with the network in place of
- *   F_true, f_true. */
+ *   F_true, f_true.
+ * dmpc_mlp_param_grad: the gradient of a loss L(f) of dmpc_mlp_rollout_linearize's f with respect to the weights, F_t held
+ *   constant at the value of the live Jacobian (mpc/approximate.py:77-119).  x [T,B,nx] are the states that launch stored,
+ *   grad_f [T-1,B,nx] = dL/df (may be NULL when T = 1).  dW1 [n_hidden,ns], db1 [n_hidden], dW2 [nx,n_hidden], db2 [nx] are
+ *   WRITTEN (not added to): sum over t and b of r a_t^T, r, delta z_t^T, delta with r = grad_f_t and
+ *   delta = (1 - a_t^2) * (W2^T r).  d_x_init [B,nx] and d_u [T,B,nu], each or NULL, are written too: they are exact zeros,
+ *   because the derivative of next through [x_t;u_t] and F_t's cancel at every step.  Two launches: one wavefront walks
+ *   trajectories w, w + G, ... (G = dmpc_mlp_param_grad_partials(B) = min(B, 512), a function of B alone) and stores one
+ *   partial into ws; the second adds the G partials per element in ascending order.  No atomics: the result is bit-equal
+ *   from call to call and depends on (T, B, nx, nu, n_hidden) and the data alone.  ws: device memory of at least
+ *   dmpc_mlp_param_grad_workspace_bytes (0 for a size the kernels refuse), else DMPC_E_WORKSPACE; not needed when T = 1,
+ *   which only zeroes the outputs.  No allocation, no host synchronisation. */
 int dmpc_mlp_dx_supported(int nx, int nu, int n_hidden, int act);
 int dmpc_mlp_rollout_linearize(int T, int B, int nx, int nu, int n_hidden, int act, int residual, const float *W1,
                                const float *b1, const float *W2, const float *b2, const float *x_init, const float *u,
@@ -325,6 +336,12 @@ int dmpc_mpc_forward_rec_mlp(int T, int B, int nx, int nu, int n_hidden, int act
                              const float *C_true, const float *c_true, float ls_decay, int max_ls_iter, float *x_out,
                              float *u_out, float *costs, float *old_costs, float *alphas, float *objs, float *u_first,
                              int32_t *n_ls_iter, int32_t *info, dmpc_stream_t stream);
+int dmpc_mlp_param_grad_partials(int B);
+size_t dmpc_mlp_param_grad_workspace_bytes(int B, int nx, int nu, int n_hidden);
+int dmpc_mlp_param_grad(int T, int B, int nx, int nu, int n_hidden, int act, int residual, const float *W1,
+                        const float *b1, const float *W2, const float *b2, const float *x, const float *u,
+                        const float *grad_f, float *dW1, float *db1, float *dW2, float *db2, float *d_x_init, float *d_u,
+                        void *ws, size_t ws_bytes, dmpc_stream_t stream);
 
 /* Nominal rollout under a LinDx (util.py:239-277 get_traj): x_0 = x_init, x_{t+1} = F_t [x_t; u_t] + f_t (f may be
  * NULL), with the summation order of the MPC step's own line-search rollout - so that a trajectory re-rolled from

@@ -140,7 +140,26 @@ int main() {
               EXPECT(dmpc_mpc_forward_rec_mlp(T, 5, nx, nu, H, 0, 1, p, p, p, p, p, p, p, nullptr, p, p, p, p, 0.2f, 10, p, p, p, p,
                                               p, p, p, pi, pi, nullptr) == DMPC_E_BADARG);
             }
+            // its weight gradient: the same order of checks, then the workspace
+            const size_t gwb = dmpc_mlp_param_grad_workspace_bytes(5, nx, nu, H);
+            EXPECT((gwb > 0) == (sized && nx <= 16 && nu <= 8 && H >= 1 && H <= 256));
+            EXPECT(gwb == (size_t)dmpc_mlp_param_grad_partials(5) * (size_t)(gwb ? H * (nx + nu) + H + nx * H + nx : 0) * sizeof(float));
+            const int rg = dmpc_mlp_param_grad(T, 5, nx, nu, H, act, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, ws, gwb, nullptr);
+            if (!sized || T <= 0) EXPECT(rg == DMPC_E_BADARG);
+            else if (!ok) EXPECT(rg == DMPC_E_UNSUPPORTED);
+            else EXPECT(rg >= 0);
+            if (ok && T > 1) {
+              EXPECT(dmpc_mlp_param_grad(T, 5, nx, nu, H, 0, 1, nullptr, p, p, p, p, p, p, p, p, p, p, p, p, ws, gwb, nullptr) ==
+                     DMPC_E_BADARG);
+              EXPECT(dmpc_mlp_param_grad(T, 5, nx, nu, H, 0, 1, p, p, p, p, p, p, p, p, p, nullptr, p, p, p, ws, gwb, nullptr) ==
+                     DMPC_E_BADARG);
+              EXPECT(dmpc_mlp_param_grad(T, 5, nx, nu, H, 0, 1, p, p, p, p, p, p, p, p, p, p, p, nullptr, nullptr, ws, gwb - 1,
+                                         nullptr) == DMPC_E_WORKSPACE);
+              EXPECT(dmpc_mlp_param_grad(T, 5, nx, nu, H, 0, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, nullptr, gwb, nullptr) ==
+                     DMPC_E_WORKSPACE);
+            }
           }
+  EXPECT(dmpc_mlp_param_grad_partials(0) == 0 && dmpc_mlp_param_grad_partials(1 << 30) == dmpc_mlp_param_grad_partials(1 << 20));
   EXPECT(dmpc_lqr_shared_workspace_bytes(0, 1, 1, 1) == 0 && dmpc_lqr_shared_saved_bytes(0, 1, 1) == 0);
   EXPECT(dmpc_lqr_kernel_family(0, 3) == DMPC_E_UNSUPPORTED);
   EXPECT(dmpc_lqr_workspace_bytes(0, 1, 1, 1) == 0);

@@ -5,7 +5,12 @@
 Medians over `--iters` solves after warm-up (device events around the whole solve, host time included), the number of
 kernel launches of one solve of each, and how far the two solutions' costs are apart.
 
-    python scripts/mlp_dx_timing.py [--iters 20] [--warmup 3] [--cases 3x1x32,8x2x64] [--batch 128] [--horizon 20] [--json out]"""
+`--grad` times learning instead: one `BoxDDP(update_dynamics=True, detach_unconverged=False)` solve with grad enabled plus
+`backward` of sum(x) + sum(u), for `MlpDx(device_grad=True)` (the gradient node's backward is `dmpc_mlp_param_grad`) and
+`device_grad=False` (a live torch rollout and autograd through it: the baseline) on equal weights in the same run.
+
+    python scripts/mlp_dx_timing.py [--grad] [--iters 20] [--warmup 3] [--cases 3x1x32,8x2x64] [--batch 128] [--horizon 20]
+                                    [--json out]"""
 import argparse
 import json
 import os
@@ -71,8 +76,60 @@ def run_case(nx, nu, H, B, T, iters, warmup):
     return out
 
 
+def run_grad_case(nx, nu, H, B, T, iters, warmup):
+    """both routes on equal weights, alternating solve by solve; per route the median of solve + backward and of the
+    backward alone (device events, host time included), the launches of one solve + backward, the sampled clocks"""
+    from bench import ClockSampler
+    p = synthetic.make_lqr_problem(B, T, nx, nu, seed=1)
+    dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device="cuda")   # noqa: E731
+    x0, cost = dev(p["x_init"]), QuadCost(dev(p["C"]), dev(p["c"]))
+    out = dict(nx=nx, nu=nu, n_hidden=H, B=B, T=T, leg="grad", rounds=iters)
+    routes = {}
+    for tag, flag in (("device_grad", True), ("live", False)):
+        m = MlpDx(nx, nu, H, seed=0, device_grad=flag).cuda()
+        solver = BoxDDP(T, -0.5, 0.5, B, nx, nu, None, max_iter=10, quiet=True, update_dynamics=True, detach_unconverged=False)
+        routes[tag] = (m, solver, [], [])
+
+    def once(tag, record=True):
+        m, solver, total, back = routes[tag]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        m.zero_grad(set_to_none=True)
+        ev[0].record()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            x, u, _ = solver((x0, cost, m))
+        ev[1].record()
+        (x.sum() + u.sum()).backward()
+        ev[2].record()
+        ev[2].synchronize()
+        if record:
+            total.append(ev[0].elapsed_time(ev[2]))
+            back.append(ev[1].elapsed_time(ev[2]))
+
+    for _ in range(warmup):
+        for tag in routes:
+            once(tag, record=False)
+    with ClockSampler() as clocks:
+        for _ in range(iters):
+            for tag in routes:
+                once(tag)
+    summary = clocks.summary() or {}          # hwmon sclk / mclk / power during the timed rounds; null where not shown
+    out["clocks"] = {k: summary.get(k) for k in ("sclk_mhz", "mclk_mhz", "power_w")}
+    for tag, (m, solver, total, back) in routes.items():
+        out[tag + "_ms"], out[tag + "_backward_ms"] = sorted(total)[len(total) // 2], sorted(back)[len(back) // 2]
+        out[tag + "_min_ms"] = min(total)
+        out[tag + "_launches"] = count_launches(lambda: once(tag, record=False))
+        out[tag + "_n_iter"] = solver.n_iter
+    out["speedup"] = out["live_ms"] / out["device_grad_ms"]
+    out["backward_speedup"] = out["live_backward_ms"] / out["device_grad_backward_ms"]
+    out["grads_max_rel_diff"] = max(float(((a.grad - b.grad).abs() / b.grad.abs().clamp(min=1.0)).max())
+                                    for a, b in zip(routes["device_grad"][0].parameters(), routes["live"][0].parameters()))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--grad", action="store_true")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cases", default="3x1x32,8x2x64")
@@ -83,7 +140,7 @@ def main():
     res = []
     for c in a.cases.split(","):
         nx, nu, H = (int(v) for v in c.split("x"))
-        r = run_case(nx, nu, H, a.batch, a.horizon, max(a.iters, 20), a.warmup)
+        r = (run_grad_case if a.grad else run_case)(nx, nu, H, a.batch, a.horizon, max(a.iters, 20), a.warmup)
         print(json.dumps(r), flush=True)
         res.append(r)
     if a.json:
