@@ -161,12 +161,112 @@ def cases():
     return out
 
 
+class TorchArrays:
+    """the arrays of a case as the recording makes them: one zero-filled torch tensor each.  `call` below asks for its arrays
+    through these methods; tests/arena.py's Builder has the same ones and puts them into one guarded allocation instead."""
+
+    def __init__(self, device):
+        import torch
+        self.torch, self.device = torch, device
+
+    def inp(self, name, array, dtype=np.float32):
+        return self.torch.as_tensor(np.asarray(array, dtype=dtype), device=self.device)
+
+    def out(self, name, shape, dtype=np.float32):
+        return self.torch.zeros(tuple(shape), dtype=getattr(self.torch, np.dtype(dtype).name), device=self.device)
+
+    produced = out      # an input of the call that a preparing call writes
+    pre = out           # an output of a preparing call that the call itself does not see
+
+    def info(self, name, n, written=False):
+        return self.torch.zeros(n, dtype=self.torch.int32, device=self.device)
+
+    def ws(self, name, nbytes):
+        return self.torch.zeros(max(nbytes, 16), dtype=self.torch.uint8, device=self.device)
+
+    @staticmethod
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+
+def call(c, lib, al):
+    """the arrays of case c from the allocator `al` -> (prepare, fn): `fn(ptr)` makes the case's call and returns its code,
+    `prepare(ptr)` - or None - the saving solve whose blocks it reads; `ptr` turns an array of `al` into its device pointer"""
+    T, B, nx, nu, ns = c["T"], c["B"], c["nx"], c["nu"], c["nx"] + c["nu"]
+    from chainer_differentiable_mpc_amd import synthetic
+    p = synthetic.make_lqr_problem(B, T, nx, nu, seed=5, with_f=c.get("has_f", True))
+    fn = c["fn"]
+    d = {k: (None if v is None or v.size == 0 else al.inp(k, v)) for k, v in p.items()}
+    mask = None
+    if c.get("mask"):
+        mask = al.inp("mask", (np.arange(T * B * nu).reshape(T, B, nu) % 3 == 0), dtype=np.uint8)
+    need = lib.dmpc_lqr_workspace_bytes(T, B, nx, nu)
+    head = (T, B, nx, nu)
+    if fn in ("solve", "backward_ws", "backward", "forward"):
+        info = al.info("info", B)
+        if fn == "solve":
+            g = c.get("gains", False)
+            Ks, ks = (al.out("Ks", (T, B, nu, nx)), al.out("ks", (T, B, nu))) if g else (None, None)
+            x, u = al.out("x", (T, B, nx)), al.out("u", (T, B, nu))
+            ws = al.ws("ws", need) if c.get("has_ws", True) else None
+            return None, lambda ptr: lib.dmpc_lqr_solve(*head, ptr(d["C"]), ptr(d["c"]), ptr(d["F"]), ptr(d["f"]), ptr(d["x_init"]),
+                                                        ptr(mask), ptr(Ks), ptr(ks), ptr(x), ptr(u), ptr(ws),
+                                                        need if ws is not None else 0, ptr(info), None)
+        if fn == "forward":
+            Ks, ks = al.inp("Ks", np.zeros((T, B, nu, nx))), al.inp("ks", np.zeros((T, B, nu)))
+            x, u = al.out("x", (T, B, nx)), al.out("u", (T, B, nu))
+            return None, lambda ptr: lib.dmpc_lqr_forward_sweep(*head, ptr(Ks), ptr(ks), ptr(d["F"]), ptr(d["f"]), ptr(d["x_init"]),
+                                                                ptr(mask), ptr(x), ptr(u), ptr(info), None)
+        Ks, ks = al.out("Ks", (T, B, nu, nx)), al.out("ks", (T, B, nu))
+        if fn == "backward_ws":
+            ws = al.ws("ws", need)
+            return None, lambda ptr: lib.dmpc_lqr_backward_sweep_ws(*head, ptr(d["C"]), ptr(d["c"]), ptr(d["F"]), ptr(d["f"]), ptr(mask),
+                                                                    ptr(Ks), ptr(ks), ptr(ws), need, ptr(info), None)
+        return None, lambda ptr: lib.dmpc_lqr_backward_sweep(*head, ptr(d["C"]), ptr(d["c"]), ptr(d["F"]), ptr(d["f"]), ptr(mask),
+                                                             ptr(Ks), ptr(ks), ptr(info), None)
+    # the saving solve, as the call itself or as the one that leaves the blocks the call reads (zeros where it does not serve
+    # the size)
+    last = fn == "solve_saving"
+    made = al.out if last else al.produced
+    Ks, ks = made("Ks", (T, B, nu, nx)), (al.out if last else al.pre)("ks", (T, B, nu))
+    Quu, Qxu = made("Quu", (T, B, nu, nu)), made("Qxu", (T, B, nx, nu))
+    Vv = (al.pre if fn == "saved_solve" else made)("Vv", (T, B, nx, nx + 1))
+    x, u = ((al.pre, al.pre) if fn == "saved_solve" else (made, made))
+    x, u = x("x", (T, B, nx)), u("u", (T, B, nu))
+    info = al.info("info", B, written=last)
+
+    def saving(ptr):
+        return lib.dmpc_lqr_solve_saving(*head, ptr(d["C"]), ptr(d["c"]), ptr(d["F"]), ptr(d["f"]), ptr(d["x_init"]), ptr(Ks), ptr(ks),
+                                         ptr(Quu), ptr(Qxu), ptr(Vv), ptr(x), ptr(u), ptr(info), None)
+    if last:
+        return None, saving
+    if fn == "saved_solve":
+        c2 = al.inp("c2", np.random.RandomState(7).randn(T, B, ns))
+        x2, u2 = al.out("x2", (T, B, nx)), al.out("u2", (T, B, nu))
+        return saving, lambda ptr: lib.dmpc_lqr_saved_solve(*head, ptr(c2), ptr(d["F"]), ptr(Ks), ptr(Quu), ptr(Qxu), ptr(d["x_init"]),
+                                                            ptr(x2), ptr(u2), ptr(info), None)
+    rng = np.random.RandomState(9)
+    gx, gu = al.inp("gx", rng.randn(T, B, nx)), al.inp("gu", rng.randn(T, B, nu))
+    dx0, dC, dc = al.out("dx0", (B, nx)), al.out("dC", (T, B, ns, ns)), al.out("dc", (T, B, ns))
+    dF, df = al.out("dF", (T - 1, B, nx, ns)), al.out("df", (T - 1, B, nx))
+    kneed = lib.dmpc_lqr_kkt_workspace_bytes(T, B, nx, nu)
+    kws = al.ws("kws", kneed)
+    tail = lambda ptr: (0, ptr(dx0), ptr(dC), ptr(dc), ptr(dF), ptr(df), ptr(kws), kneed, ptr(info), None)   # noqa: E731
+    if fn == "kkt_grad_saved":
+        vv = Vv if c.get("has_vv", True) else None
+        return saving, lambda ptr: lib.dmpc_lqr_kkt_grad_saved(*head, ptr(d["C"]), ptr(d["c"]), ptr(d["F"]), ptr(x), ptr(u), ptr(Ks),
+                                                               ptr(Quu), ptr(Qxu), ptr(vv), ptr(gx), ptr(gu), *tail(ptr))
+    assert fn == "kkt_grad"
+    return saving, lambda ptr: lib.dmpc_lqr_kkt_grad(*head, ptr(d["C"]), ptr(d["c"]), ptr(d["F"]), ptr(x), ptr(u), ptr(gx), ptr(gu),
+                                                     *tail(ptr))
+
+
 def run_cases():
     """-> [{id, rc, kernel}]; kernel None: the call launched nothing"""
     import torch
 
     sys.path.insert(0, ROOT)
-    from chainer_differentiable_mpc_amd import _lib, synthetic
+    from chainer_differentiable_mpc_amd import _lib
 
     lib = _lib.load()
     dev = torch.device("cuda:0")
@@ -176,10 +276,6 @@ def run_cases():
     def empty(*shape):
         return torch.zeros(shape, **f32)
 
-    def problem(c):
-        p = synthetic.make_lqr_problem(c["B"], c["T"], c["nx"], c["nu"], seed=5, with_f=c.get("has_f", True))
-        return {k: (None if v is None else torch.as_tensor(v, **f32)) for k, v in p.items()}
-
     def sentinel():
         # a launch no case of the table makes: a call that leaves its name behind launched nothing
         Ks, ks, x0, x, u = empty(1, 1, 1, 2), empty(1, 1, 1), empty(1, 2), empty(1, 1, 2), empty(1, 1, 1)
@@ -187,72 +283,18 @@ def run_cases():
         assert rc == 0
         return _lib.last_kernel_name()
 
-    def call(c):
-        T, B, nx, nu, ns = c["T"], c["B"], c["nx"], c["nu"], c["nx"] + c["nu"]
-        d = problem(c)
-        F = ptr(d["F"]) if T > 1 else None
-        mask = None
-        if c.get("mask"):
-            mask = torch.as_tensor((np.arange(T * B * nu).reshape(T, B, nu) % 3 == 0).astype(np.uint8), device=dev)
-        Ks, ks, x, u = empty(T, B, nu, nx), empty(T, B, nu), empty(T, B, nx), empty(T, B, nu)
-        info = torch.zeros(B, dtype=torch.int32, device=dev)
-        need = lib.dmpc_lqr_workspace_bytes(T, B, nx, nu)
-        ws = torch.zeros(max(need, 16), dtype=torch.uint8, device=dev) if c.get("has_ws", True) else None
-        keep = [d, mask, Ks, ks, x, u, info, ws]
-        head = (T, B, nx, nu)
-        fn = c["fn"]
-        if fn == "solve":
-            g = c.get("gains", False)
-            return keep, lambda: lib.dmpc_lqr_solve(*head, ptr(d["C"]), ptr(d["c"]), F, ptr(d["f"]), ptr(d["x_init"]), ptr(mask),
-                                                    ptr(Ks) if g else None, ptr(ks) if g else None, ptr(x), ptr(u), ptr(ws),
-                                                    need if ws is not None else 0, ptr(info), None)
-        if fn == "backward_ws":
-            return keep, lambda: lib.dmpc_lqr_backward_sweep_ws(*head, ptr(d["C"]), ptr(d["c"]), F, ptr(d["f"]), ptr(mask), ptr(Ks),
-                                                                ptr(ks), ptr(ws), need, ptr(info), None)
-        if fn == "backward":
-            return keep, lambda: lib.dmpc_lqr_backward_sweep(*head, ptr(d["C"]), ptr(d["c"]), F, ptr(d["f"]), ptr(mask), ptr(Ks),
-                                                             ptr(ks), ptr(info), None)
-        if fn == "forward":
-            return keep, lambda: lib.dmpc_lqr_forward_sweep(*head, ptr(Ks), ptr(ks), F, ptr(d["f"]), ptr(d["x_init"]), ptr(mask),
-                                                            ptr(x), ptr(u), ptr(info), None)
-        Quu, Qxu, Vv = empty(T, B, nu, nu), empty(T, B, nx, nu), empty(T, B, nx, nx + 1)
-        keep += [Quu, Qxu, Vv]
-
-        def saving():
-            return lib.dmpc_lqr_solve_saving(*head, ptr(d["C"]), ptr(d["c"]), F, ptr(d["f"]), ptr(d["x_init"]), ptr(Ks), ptr(ks),
-                                             ptr(Quu), ptr(Qxu), ptr(Vv), ptr(x), ptr(u), ptr(info), None)
-        if fn == "solve_saving":
-            return keep, saving
-        saving()                     # (the saved blocks the next call reads; zeros where the saving solve does not serve the size)
-        torch.cuda.synchronize()
-        if fn == "saved_solve":
-            c2 = torch.as_tensor(np.random.RandomState(7).randn(T, B, ns), **f32)
-            x2, u2 = empty(T, B, nx), empty(T, B, nu)
-            keep += [c2, x2, u2]
-            return keep, lambda: lib.dmpc_lqr_saved_solve(*head, ptr(c2), F, ptr(Ks), ptr(Quu), ptr(Qxu), ptr(d["x_init"]), ptr(x2),
-                                                          ptr(u2), ptr(info), None)
-        rng = np.random.RandomState(9)
-        gx, gu = torch.as_tensor(rng.randn(T, B, nx), **f32), torch.as_tensor(rng.randn(T, B, nu), **f32)
-        dx0, dC, dc, dF, df = empty(B, nx), empty(T, B, ns, ns), empty(T, B, ns), empty(T - 1, B, nx, ns), empty(T - 1, B, nx)
-        kneed = lib.dmpc_lqr_kkt_workspace_bytes(T, B, nx, nu)
-        kws = torch.zeros(max(kneed, 16), dtype=torch.uint8, device=dev)
-        keep += [gx, gu, dx0, dC, dc, dF, df, kws]
-        tail = (0, ptr(dx0), ptr(dC), ptr(dc), ptr(dF), ptr(df), ptr(kws), kneed, ptr(info), None)
-        if fn == "kkt_grad_saved":
-            vv = ptr(Vv) if c.get("has_vv", True) else None
-            return keep, lambda: lib.dmpc_lqr_kkt_grad_saved(*head, ptr(d["C"]), ptr(d["c"]), F, ptr(x), ptr(u), ptr(Ks), ptr(Quu),
-                                                             ptr(Qxu), vv, ptr(gx), ptr(gu), *tail)
-        assert fn == "kkt_grad"
-        return keep, lambda: lib.dmpc_lqr_kkt_grad(*head, ptr(d["C"]), ptr(d["c"]), F, ptr(x), ptr(u), ptr(gx), ptr(gu), *tail)
-
     rows = []
     for c in cases():
-        keep, fn = call(c)
+        al = TorchArrays(dev)
+        prepare, fn = call(c, lib, al)
+        if prepare is not None:
+            prepare(al.ptr)          # (the saved blocks the call reads)
+            torch.cuda.synchronize()
         idle = sentinel()
-        rc = fn()
+        rc = fn(al.ptr)
         name = _lib.last_kernel_name()
         torch.cuda.synchronize()
-        del keep
+        del al, prepare, fn
         rows.append(dict(id=c["id"], rc=int(rc), kernel=None if name == idle else name))
     return rows
 

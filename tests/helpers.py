@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests."""
+import importlib.util
 import os
 
 import numpy as np
@@ -92,3 +93,25 @@ def assert_step_close(got_u, got_x, ref_u, ref_x, old_costs, ref_costs, candidat
         assert (best <= tol).all(), "%s: tie rows %s match no candidate of the line search (worst %.2e)" % (
             what, rows[best > tol][:8], best.max())
     return int(ties.sum()), forked
+
+
+def load_routes_script():
+    """tests/golden/make_lqr_routes.py as a module (its grids, its case table, its recordings)"""
+    spec = importlib.util.spec_from_file_location("make_lqr_routes", os.path.join(GOLDEN, "make_lqr_routes.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+# ((T, B, nx, nu), kernel): one case per kernel the co-state sweep can take (tests/test_kkt_gpu.py by name and against the
+# oracle, tests/abi_calls.py inside a guarded arena)
+COSTATE_PATHS = [((4, 8, 3, 1), "void dmpc::costate_dma_kernel<3, 1, 4>"),             # 16 lanes, LDS-DMA ring
+                 ((4, 6, 3, 1), "void dmpc::costate_kernel<3, 1, 16, false>"),         # ragged batch: register prefetch
+                 ((5, 8, 3, 3), "void dmpc::costate_kernel<4, 4, 16, true>"),          # 16-lane container
+                 ((3, 8, 12, 8), "void dmpc::costate_wide_kernel<12, 8, 2, false, 4>"),   # wide, exact
+                 ((3, 8, 9, 4), "void dmpc::costate_wide_kernel<16, 4, 2, true, 4>"),     # wide, padded
+                 ((3, 8, 14, 6), "void dmpc::costate_wide_kernel<16, 8, 2, true, 3>"),    # wide, padded, three wavefronts
+                 ((3, 5, 14, 6), "dmpc::costate_staged_kernel"),                          # ragged batch of a wide shape
+                 ((3, 3, 20, 6), "dmpc::costate_staged_kernel"),                          # 17+ states
+                 ((3, 4, 32, 8), "void dmpc::costate_kernel<32, 8, 64, false>"),       # a wavefront per trajectory
+                 ((3, 4, 40, 30), "dmpc::costate_generic_kernel")]                        # more than 63 elements of tau
