@@ -1,8 +1,10 @@
 // mlp_dx_api.hip - C-ABI entry points of the learned one-hidden-layer dynamics model (include/dmpc.h section E,
 // "MlpDx"): the nominal rollout with its analytic linearisation, MPCstep.forward_rec with the network as the true
 // dynamics, and the gradient of the linearisation's f with respect to the weights.  Every argument and size check comes
-// before the first HIP call.
+// before the first HIP call.  The activation is a template parameter of the kernels; mlp_with_act picks the instance.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../../include/dmpc.h"
 #include "api_util.hpp"
@@ -13,9 +15,20 @@ namespace dmpc {
 // 0: launch; DMPC_E_BADARG / DMPC_E_UNSUPPORTED otherwise
 static int mlp_check(int nx, int nu, int n_hidden, int act) {
   if (nx <= 0 || nu <= 0) return DMPC_E_BADARG;
-  if (act != 0) return DMPC_E_UNSUPPORTED;
+  if (act != kMlpActTanh && act != kMlpActRelu && act != kMlpActSilu && act != kMlpActSoftplus) return DMPC_E_UNSUPPORTED;
   if (nx > kMlpMaxNx || nu > kMlpMaxNu || n_hidden < 1 || n_hidden > kMlpMaxHidden) return DMPC_E_UNSUPPORTED;
   return 0;
+}
+
+// fn(std::integral_constant<int, ACT>) for an `act` that mlp_check has passed
+template <typename Fn>
+static void mlp_with_act(int act, Fn &&fn) {
+  switch (act) {
+    case kMlpActRelu: fn(std::integral_constant<int, kMlpActRelu>{}); break;
+    case kMlpActSilu: fn(std::integral_constant<int, kMlpActSilu>{}); break;
+    case kMlpActSoftplus: fn(std::integral_constant<int, kMlpActSoftplus>{}); break;
+    default: fn(std::integral_constant<int, kMlpActTanh>{}); break;
+  }
 }
 
 }  // namespace dmpc
@@ -36,8 +49,10 @@ int dmpc_mlp_rollout_linearize(int T, int B, int nx, int nu, int n_hidden, int a
   if (rc != 0) return rc;
   if ((size_t)T * B * nx * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;
   MlpRolloutArgs ra{T, B, MlpModel{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2}, x_init, u, x_out, F_out, f_out};
-  DMPC_LAUNCH_GGL(mlp_rollout_linearize_kernel, dim3((B + kMlpWaves - 1) / kMlpWaves), dim3(64 * kMlpWaves),
-                  mlp_lds_bytes(nx, nu, n_hidden), static_cast<hipStream_t>(stream_), ra);
+  mlp_with_act(act, [&](auto A) {
+    DMPC_LAUNCH_GGL(mlp_rollout_linearize_kernel<decltype(A)::value>, dim3((B + kMlpWaves - 1) / kMlpWaves),
+                    dim3(64 * kMlpWaves), mlp_lds_bytes(nx, nu, n_hidden), static_cast<hipStream_t>(stream_), ra);
+  });
   return (int)hipGetLastError();
 }
 
@@ -57,8 +72,10 @@ int dmpc_mpc_forward_rec_mlp(int T, int B, int nx, int nu, int n_hidden, int act
   MpcFwdArgs fa{T, B, Ks, ks, controls, states, u_lower, u_upper, C_true, c_true, nullptr, nullptr, ls_decay,
                 max_ls_iter, /*ls_cap=*/64, x_out, u_out, u_first, costs, old_costs, alphas, objs, n_ls_iter, info};
   const MlpModel m{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2};
-  DMPC_LAUNCH_GGL(mpc_forward_rec_mlp_kernel, dim3((B + kMlpWaves - 1) / kMlpWaves), dim3(64 * kMlpWaves),
-                  mlp_lds_bytes(nx, nu, n_hidden), static_cast<hipStream_t>(stream_), fa, m);
+  mlp_with_act(act, [&](auto A) {
+    DMPC_LAUNCH_GGL(mpc_forward_rec_mlp_kernel<decltype(A)::value>, dim3((B + kMlpWaves - 1) / kMlpWaves),
+                    dim3(64 * kMlpWaves), mlp_lds_bytes(nx, nu, n_hidden), static_cast<hipStream_t>(stream_), fa, m);
+  });
   return (int)hipGetLastError();
 }
 
@@ -90,8 +107,10 @@ int dmpc_mlp_param_grad(int T, int B, int nx, int nu, int n_hidden, int act, int
   } else {
     MlpGradArgs ga{T, B, G, MlpModel{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2}, x, u, grad_f,
                    static_cast<float *>(ws), d_x_init, d_u};
-    DMPC_LAUNCH_GGL(mlp_param_grad_kernel, dim3((G + kMlpWaves - 1) / kMlpWaves), dim3(64 * kMlpWaves),
-                    mlp_lds_bytes(nx, nu, n_hidden), stream, ga);
+    mlp_with_act(act, [&](auto A) {
+      DMPC_LAUNCH_GGL(mlp_param_grad_kernel<decltype(A)::value>, dim3((G + kMlpWaves - 1) / kMlpWaves),
+                      dim3(64 * kMlpWaves), mlp_lds_bytes(nx, nu, n_hidden), stream, ga);
+    });
   }
   MlpGradReduceArgs rd{G, nx, nu, n_hidden, static_cast<const float *>(ws), dW1, db1, dW2, db2};
   DMPC_LAUNCH_GGL(mlp_param_grad_reduce_kernel, dim3((mlp_grad_partial_floats(nx, nu, n_hidden) + 255) / 256), dim3(256), 0,

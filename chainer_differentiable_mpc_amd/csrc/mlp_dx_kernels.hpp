@@ -1,9 +1,12 @@
 // mlp_dx_kernels.hpp - a learned one-hidden-layer dynamics model on the device (MlpDx of the Python layer):
 //
-//     next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual),     act = tanh
+//     next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual),     act = tanh | relu | silu | softplus
+//
+// The activation is a template parameter of the three kernels that evaluate the network (mlp_act below is the only place
+// where it is looked at): a = act(z) and d = act'(z) of the pre-activation z = W1 [x;u] + b1.
 //
 //   mlp_rollout_linearize_kernel   get_traj + linearize_dynamics (util.py:239-277, mpc/approximate.py:77-119) in one
-//                                  launch: x_{t+1} = next(x_t, u_t), F_t = [I|0] residual + W2 diag(1 - a^2) W1,
+//                                  launch: x_{t+1} = next(x_t, u_t), F_t = [I|0] residual + W2 diag(d) W1,
 //                                  f_t = next - F_t [x_t;u_t].
 //   mpc_forward_rec_mlp_kernel     MPCstep.forward_rec (mpc/mpc_step.py:175-286) with the network as the TRUE dynamics:
 //                                  the clamped closed-loop rollout and per-trajectory line search of
@@ -18,7 +21,7 @@
 //     W2s [nx][H | 1]   lanes read consecutive units of a row (no conflict); the odd stride separates the rows that the
 //                       Jacobian's lanes read at once
 //     b1s [H], b2s [nx]
-// 25.6 + 16.4 + 1.1 KB at the largest size.  Behind them every wavefront has 672 floats of its own (1 - a^2 per hidden
+// 25.6 + 16.4 + 1.1 KB at the largest size.  Behind them every wavefront has 672 floats of its own (d per hidden
 // unit, the step's Jacobian).  Element i of tau = [x;u] lives in lane i; a value another lane needs is read from that
 // lane's register (v_readlane), never through LDS, so the search needs no barrier after the staging one and its
 // wavefronts leave the loop one by one.
@@ -26,7 +29,8 @@
 // Bit-equal dynamics.  The search ends when a candidate collapses onto the nominal trajectory and its cost difference is
 // exactly 0 (see PendulumModel in mpc_kernels.hpp).  Both kernels evaluate the network through mlp_next alone: explicit
 // fmaf, inputs in ascending order, a lane's hidden units in ascending order, one butterfly reduction per output - an
-// order that depends on (nx, nu, H) and on nothing else: not on B, the grid, or the wavefront's slot in its workgroup.
+// order that depends on (nx, nu, H) and the activation and on nothing else: not on B, the grid, or the wavefront's slot in
+// its workgroup.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,8 +69,30 @@ __device__ __forceinline__ float lane_value(float v, int l) {   // l is wave-uni
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
 }
 
-// THE activation (act 0 of the C ABI)
-__device__ __forceinline__ float mlp_act(float z) { return tanhf(z); }
+// the `act` codes of the C ABI (include/dmpc.h; 1 is never assigned)
+constexpr int kMlpActTanh = 0, kMlpActRelu = 2, kMlpActSilu = 3, kMlpActSoftplus = 4;
+
+// THE activation: a = act(z) and d = act'(z), the only place a network's nonlinearity is evaluated.  expf / log1pf, not
+// the fast intrinsics.  A NaN z gives a NaN a for every activation (relu included: `z <= 0` is false for a NaN), so the
+// search's is_finite tests see what they see for tanh.  relu'(0) = 0, torch's convention.
+template <int ACT>
+__device__ __forceinline__ void mlp_act(const float z, float &a, float &d) {
+  static_assert(ACT == kMlpActTanh || ACT == kMlpActRelu || ACT == kMlpActSilu || ACT == kMlpActSoftplus, "activation");
+  if constexpr (ACT == kMlpActTanh) {
+    a = tanhf(z);
+    d = fmaf(-a, a, 1.0f);
+  } else if constexpr (ACT == kMlpActRelu) {
+    a = z <= 0.f ? 0.f : z;
+    d = z > 0.f ? 1.f : 0.f;
+  } else if constexpr (ACT == kMlpActSilu) {
+    const float s = 1.0f / (1.0f + expf(-z));
+    a = z * s;
+    d = s * (1.0f + z * (1.0f - s));
+  } else {
+    a = fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
+    d = 1.0f / (1.0f + expf(-z));
+  }
+}
 
 // every thread of the workgroup takes part, also those of wavefronts without a trajectory; ends with the one barrier
 __device__ __forceinline__ MlpLds mlp_stage(const MlpModel &m, float *lds) {
@@ -89,10 +115,12 @@ __device__ __forceinline__ MlpLds mlp_stage(const MlpModel &m, float *lds) {
 }
 
 // ONE step of the model.  tau: element `lane` of [x;u] (anything in lanes >= ns: never read).  Returns element `lane` of the
-// next state (0 in lanes >= nx) and leaves this lane's activations in a[] - 0 for units beyond H, which therefore add exact
-// zeros to every sum and whose LDS addresses are clamped into range.
+// next state (0 in lanes >= nx) and leaves this lane's activations in a[] and their derivatives in d[] - both 0 for units
+// beyond H, which therefore add exact zeros to every sum and whose LDS addresses are clamped into range.  A caller that
+// does not read d[] does not pay for it: everything here is inlined.
+template <int ACT>
 __device__ __forceinline__ float mlp_next(const MlpModel &m, const MlpLds &L, const int lane, const float tau,
-                                          float (&a)[kMlpUnits]) {
+                                          float (&a)[kMlpUnits], float (&d)[kMlpUnits]) {
   const int ns = m.nx + m.nu, H = m.n_hidden;
   const int n_units = (H + 63) / 64;
   int row[kMlpUnits];
@@ -116,7 +144,13 @@ __device__ __forceinline__ float mlp_next(const MlpModel &m, const MlpLds &L, co
     }
   }
 #pragma unroll
-  for (int k = 0; k < kMlpUnits; ++k) a[k] = (k < n_units && has[k]) ? mlp_act(z[k]) : 0.f;
+  for (int k = 0; k < kMlpUnits; ++k) {
+    float ak, dk;
+    mlp_act<ACT>(z[k], ak, dk);
+    const bool live = k < n_units && has[k];
+    a[k] = live ? ak : 0.f;
+    d[k] = live ? dk : 0.f;
+  }
   float next = 0.f;
   for (int i = 0; i < m.nx; ++i) {
     float part = 0.f;
@@ -135,18 +169,18 @@ __device__ __forceinline__ float mlp_next(const MlpModel &m, const MlpLds &L, co
 }
 
 // F = d next / d [x;u] (nx x ns, row-major) at Fp and into the wavefront's LDS, f = next - F tau at fq (lanes < nx).
-// VALU over LDS: 1 - a^2 of every hidden unit goes to the wavefront's scratch, then lane e owns entries e, e + 64, ... of F
+// VALU over LDS: d of every hidden unit goes to the wavefront's scratch, then lane e owns entries e, e + 64, ... of F
 // and sums over the hidden units in ascending order.  Within one wavefront LDS operations complete in program order; the
 // fences keep the compiler from moving a read above the write it depends on.
 __device__ __forceinline__ void mlp_jacobian_store(const MlpModel &m, const MlpLds &L, const int lane, const float tau,
-                                                   const float next, const float (&a)[kMlpUnits], float *Fp, float *fq) {
+                                                   const float next, const float (&d)[kMlpUnits], float *Fp, float *fq) {
   const int nx = m.nx, ns = m.nx + m.nu, H = m.n_hidden;
   float *g = L.wave, *Fs = L.wave + kMlpMaxHidden;
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the previous step's reads of g and Fs are done)
 #pragma unroll
   for (int k = 0; k < kMlpUnits; ++k) {
     const int h = lane + 64 * k;
-    if (h < H) g[h] = fmaf(-a[k], a[k], 1.0f);
+    if (h < H) g[h] = d[k];
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   for (int e = lane; e < nx * ns; e += 64) {
@@ -172,6 +206,7 @@ struct MlpRolloutArgs {
   float *x, *F, *f;          // [T,B,nx]; [T-1,B,nx,ns] or nullptr; [T-1,B,nx] or nullptr
 };
 
+template <int ACT>
 __global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(const MlpRolloutArgs a) {
   extern __shared__ float lds[];
   const MlpLds L = mlp_stage(a.m, lds);
@@ -187,9 +222,9 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(c
     if (lane < nx) a.x[tb * nx + lane] = xc;
     if (t == T - 1) break;
     const float tau = lane < nx ? xc : (lane < ns ? a.u[tb * nu + (lane - nx)] : 0.f);
-    float act[kMlpUnits];
-    const float xn = mlp_next(a.m, L, lane, tau, act);
-    if (a.F != nullptr) mlp_jacobian_store(a.m, L, lane, tau, xn, act, a.F + tb * nx * ns, a.f ? a.f + tb * nx : nullptr);
+    float act[kMlpUnits], dact[kMlpUnits];
+    const float xn = mlp_next<ACT>(a.m, L, lane, tau, act, dact);
+    if (a.F != nullptr) mlp_jacobian_store(a.m, L, lane, tau, xn, dact, a.F + tb * nx * ns, a.f ? a.f + tb * nx : nullptr);
     xc = xn;
   }
 }
@@ -198,6 +233,7 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(c
 // through it mpc_forward_rec_kernel's): the cost difference per timestep without cancellation, bound_tol's snap, the
 // pass cap.  a.F / a.f are not read.  The loop is wave-uniform by construction - a wavefront is one trajectory - so a
 // trajectory that has finished runs, stores and commits nothing more.
+template <int ACT>
 __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(const MpcFwdArgs a, const MlpModel m) {
   extern __shared__ float lds[];
   const MlpLds L = mlp_stage(m, lds);
@@ -264,8 +300,8 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(con
       if (n_pass == 0) old_cost += wave_sum64(part0);                                    // :191
       if (a.objs != nullptr && lane == 0) a.objs[tb] = obj;
       if (t < T - 1) {                                                                   // :237-240
-        float act[kMlpUnits];
-        xc = mlp_next(m, L, lane, tau, act);
+        float act[kMlpUnits], dact[kMlpUnits];
+        xc = mlp_next<ACT>(m, L, lane, tau, act, dact);
       }
     }
     ++n_pass;
@@ -289,13 +325,14 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(con
 
 // The gradient of L(f) with respect to W1, b1, W2, b2 for f_t = next(x_t, u_t) - F_t [x_t;u_t] along the rolled states,
 // F_t a CONSTANT with the value of the live Jacobian (MlpDx.linearize; mpc/approximate.py:77-119).  With z_t = [x_t;u_t],
-// a_t = tanh(W1 z_t + b1), g_t = dL/df_t, lam_{T-1} = 0, for t = T-2 .. 0:
+// a_t = act(W1 z_t + b1), d_t = act'(W1 z_t + b1), g_t = dL/df_t, lam_{T-1} = 0, for t = T-2 .. 0:
 //     r     = g_t + lam_{t+1}
-//     delta = (1 - a_t^2) * (W2^T r)
+//     delta = d_t * (W2^T r)
 //     dW2 += r a_t^T ;  db2 += r ;  dW1 += delta z_t^T ;  db1 += delta
-//     e     = (1 - a_t^2) * (W2^T lam_{t+1}) ;  du_t = W1[:, nx:]^T e ;  lam_t = W1[:, :nx]^T e (+ lam_{t+1} when residual)
+//     e     = d_t * (W2^T lam_{t+1}) ;  du_t = W1[:, nx:]^T e ;  lam_t = W1[:, :nx]^T e (+ lam_{t+1} when residual)
 // Every term of lam_t carries a factor lam_{t+1}, and lam_{T-1} = 0: lam_t = 0, e = 0 and du_t = 0 for every t, as exact
-// zeros in any arithmetic - next's derivative through z_t and F_t's cancel at every step, nothing is left to carry.
+// zeros in any arithmetic and for every activation - next's derivative through z_t and F_t's cancel at every step,
+// nothing is left to carry.
 // So r = g_t, the lines of e, du and lam are not evaluated, and d_x_init, d_u are stored as the zeros they are.
 //
 // One wavefront per trajectory as above; wavefront w of G serves trajectories w, w + G, ... in ascending order, t
@@ -316,6 +353,7 @@ struct MlpGradArgs {
   float *d_x_init, *d_u;         // [B,nx], [T,B,nu], each or nullptr
 };
 
+template <int ACT>
 __global__ __launch_bounds__(64 * kMlpWaves) void mlp_param_grad_kernel(const MlpGradArgs a) {
   extern __shared__ float lds[];
   const MlpLds L = mlp_stage(a.m, lds);
@@ -343,8 +381,8 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_param_grad_kernel(const Ml
       const size_t tb = (size_t)t * B + b;
       const float tau = lane < nx ? a.x[tb * nx + lane] : (lane < ns ? a.u[tb * nu + (lane - nx)] : 0.f);
       const float r = lane < nx ? a.grad_f[tb * nx + lane] : 0.f;
-      float act[kMlpUnits];
-      (void)mlp_next(a.m, L, lane, tau, act);
+      float act[kMlpUnits], dact[kMlpUnits];
+      (void)mlp_next<ACT>(a.m, L, lane, tau, act, dact);
       db2 += r;
       float s[kMlpUnits] = {};                               // W2^T r at this lane's units
 #pragma unroll
@@ -364,7 +402,7 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_param_grad_kernel(const Ml
       float delta[kMlpUnits];
 #pragma unroll
       for (int k = 0; k < kMlpUnits; ++k) {
-        delta[k] = fmaf(-act[k], act[k], 1.0f) * s[k];
+        delta[k] = dact[k] * s[k];
         db1[k] += delta[k];
       }
 #pragma unroll

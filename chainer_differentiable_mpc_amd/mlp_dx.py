@@ -1,6 +1,8 @@
 """`MlpDx` - a learned one-hidden-layer dynamics model for `BoxDDP` / `MPCstep`:
 
-    next(x, u) = W2 tanh(W1 [x;u] + b1) + b2 (+ x when residual)
+    next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual),     act = tanh (the default), relu, silu or softplus
+
+`MlpDx.from_sequential` takes the weights of a `torch.nn.Sequential(Linear, act, Linear)` trained elsewhere.
 
 `forward` is torch code (CPU and GPU tensors).  On the GPU, at a size the kernels serve (nx <= 16, nu <= 8, n_hidden <= 256),
 the nominal rollout with its analytic linearisation is one launch (`dmpc_mlp_rollout_linearize`) and `MPCstep`'s line search
@@ -15,18 +17,36 @@ is `dmpc_mlp_param_grad` (one sweep kernel, one fixed-order reduction)."""
 import math
 
 import torch
+import torch.nn.functional as F_nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .lqr_recursion import _workspace
 from .util import bmv
 
-ACT_TANH = 0     # the `act` argument of the C ABI
+ACT_TANH = 0     # the `act` argument of the C ABI (1 is never assigned)
+ACT_RELU = 2
+ACT_SILU = 3
+ACT_SOFTPLUS = 4
+ACTIVATIONS = {"tanh": ACT_TANH, "relu": ACT_RELU, "silu": ACT_SILU, "softplus": ACT_SOFTPLUS}
+
+# name -> (a(z), da/dz(z)); relu'(0) = 0 as torch has it; softplus' = sigmoid everywhere, as the kernels (torch's own is 1
+# beyond its threshold of 20, 2.1e-9 away)
+_ACT_FN = {
+    "tanh": (torch.tanh, lambda z: 1.0 - torch.tanh(z) ** 2),
+    "relu": (torch.relu, lambda z: (z > 0).to(z.dtype)),
+    "silu": (F_nn.silu, lambda z: torch.sigmoid(z) * (1.0 + z * (1.0 - torch.sigmoid(z)))),
+    "softplus": (F_nn.softplus, torch.sigmoid),
+}
+_ACT_OF_MODULE = {torch.nn.Tanh: "tanh", torch.nn.ReLU: "relu", torch.nn.SiLU: "silu", torch.nn.Softplus: "softplus"}
 
 
 class MlpDx(torch.nn.Module):
-    def __init__(self, n_state, n_ctrl, n_hidden, residual=True, seed=None, device_grad=False):
+    def __init__(self, n_state, n_ctrl, n_hidden, residual=True, seed=None, device_grad=False, activation="tanh"):
         super().__init__()
+        if activation not in ACTIVATIONS:
+            raise ValueError("MlpDx: unknown activation %r (one of %s)" % (activation, ", ".join(ACTIVATIONS)))
+        self.activation = activation
         self.device_grad = bool(device_grad)
         self.n_state, self.n_ctrl, self.n_hidden = int(n_state), int(n_ctrl), int(n_hidden)
         self.residual = bool(residual)
@@ -38,12 +58,52 @@ class MlpDx(torch.nn.Module):
         self.b2 = torch.nn.Parameter(torch.zeros(self.n_state))
         self._size_ok = None
 
+    @classmethod
+    def from_sequential(cls, net, n_state, n_ctrl, residual=True, device_grad=False):
+        """the model of a trained `torch.nn.Sequential(Linear(n_state + n_ctrl, H), act, Linear(H, n_state))` whose input is
+        [x;u], act one of Tanh, ReLU, SiLU, Softplus (beta = 1, threshold = 20).  The four tensors are copied; anything else is
+        a ValueError that names what was found."""
+        n_state, n_ctrl = int(n_state), int(n_ctrl)
+        found = "Sequential(%s)" % ", ".join(repr(m) for m in net) if isinstance(net, torch.nn.Sequential) else repr(net)
+        if not isinstance(net, torch.nn.Sequential) or len(net) != 3:
+            raise ValueError("MlpDx.from_sequential: want Sequential(Linear, activation, Linear), found " + found)
+        l1, act, l2 = net
+        if not isinstance(l1, torch.nn.Linear) or not isinstance(l2, torch.nn.Linear):
+            raise ValueError("MlpDx.from_sequential: want Sequential(Linear, activation, Linear), found " + found)
+        if l1.bias is None or l2.bias is None:
+            raise ValueError("MlpDx.from_sequential: both Linear layers need a bias, found " + found)
+        name = _ACT_OF_MODULE.get(type(act))
+        if name is None:
+            raise ValueError("MlpDx.from_sequential: activation must be Tanh, ReLU, SiLU or Softplus, found %r" % (act,))
+        if name == "softplus" and (act.beta != 1 or act.threshold != 20):
+            raise ValueError("MlpDx.from_sequential: Softplus must have beta=1, threshold=20, found %r" % (act,))
+        if l1.in_features != n_state + n_ctrl or l2.out_features != n_state or l2.in_features != l1.out_features:
+            raise ValueError("MlpDx.from_sequential: want Linear(%d, H) and Linear(H, %d), found %s"
+                             % (n_state + n_ctrl, n_state, found))
+        m = cls(n_state, n_ctrl, l1.out_features, residual=residual, device_grad=device_grad, activation=name)
+        with torch.no_grad():
+            for p, q in zip(m._weights(), (l1.weight, l1.bias, l2.weight, l2.bias)):
+                p.copy_(q.detach())
+        return m.to(device=l1.weight.device, dtype=l1.weight.dtype)
+
+    def extra_repr(self):
+        return "n_state=%d, n_ctrl=%d, n_hidden=%d, residual=%s, activation=%s, device_grad=%s" % (
+            self.n_state, self.n_ctrl, self.n_hidden, self.residual, self.activation, self.device_grad)
+
+    @property
+    def act_code(self):
+        """the `act` argument of the C ABI"""
+        return ACTIVATIONS[self.activation]
+
     def _weights(self):
         return self.W1, self.b1, self.W2, self.b2
 
+    def _pre(self, x, u):
+        """z = W1 [x;u] + b1"""
+        return torch.cat((x, u), dim=-1) @ self.W1.to(x).t() + self.b1.to(x)
+
     def _hidden(self, x, u):
-        W1, b1 = self.W1.to(x), self.b1.to(x)
-        return torch.tanh(torch.cat((x, u), dim=-1) @ W1.t() + b1)
+        return _ACT_FN[self.activation][0](self._pre(x, u))
 
     def _output(self, a, x):
         nxt = a @ self.W2.to(x).t() + self.b2.to(x)
@@ -54,19 +114,19 @@ class MlpDx(torch.nn.Module):
         assert x.shape[-1] == self.n_state and u.shape[-1] == self.n_ctrl and x.shape[:-1] == u.shape[:-1]
         return self._output(self._hidden(x, u), x)
 
-    def _jacobian(self, a):
-        """d next / d [x;u] at the hidden activations a [B,H] -> [B,nx,ns], a constant of the graph"""
-        a = a.detach()
-        F = torch.einsum("ih,bh,hj->bij", self.W2.detach().to(a), 1.0 - a * a, self.W1.detach().to(a))
+    def _jacobian(self, z):
+        """d next / d [x;u] at the pre-activations z [B,H] -> [B,nx,ns], a constant of the graph"""
+        z = z.detach()
+        F = torch.einsum("ih,bh,hj->bij", self.W2.detach().to(z), _ACT_FN[self.activation][1](z), self.W1.detach().to(z))
         if self.residual:
-            F = F + torch.eye(self.n_state, self.n_state + self.n_ctrl, dtype=a.dtype, device=a.device)
+            F = F + torch.eye(self.n_state, self.n_state + self.n_ctrl, dtype=z.dtype, device=z.device)
         return F
 
     # ------------------------------------------------------------------ the device path
     def supported(self):
         """the kernels serve this size (asked of the library once; nothing is launched)"""
         if self._size_ok is None:
-            self._size_ok = bool(_lib.load().dmpc_mlp_dx_supported(self.n_state, self.n_ctrl, self.n_hidden, ACT_TANH))
+            self._size_ok = bool(_lib.load().dmpc_mlp_dx_supported(self.n_state, self.n_ctrl, self.n_hidden, self.act_code))
         return self._size_ok
 
     def _on_device(self, x_init, u):
@@ -103,7 +163,7 @@ class MlpDx(torch.nn.Module):
         F = torch.empty((max(T - 1, 0), B, nx, nx + nu), dtype=torch.float32, device=d) if want_model else None
         f = torch.empty((max(T - 1, 0), B, nx), dtype=torch.float32, device=d) if want_model else None
         with _lib.guard(d):
-            rc = lib.dmpc_mlp_rollout_linearize(T, B, nx, nu, self.n_hidden, ACT_TANH, int(self.residual), _lib.ptr(W1),
+            rc = lib.dmpc_mlp_rollout_linearize(T, B, nx, nu, self.n_hidden, self.act_code, int(self.residual), _lib.ptr(W1),
                                                 _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), _lib.ptr(x0), _lib.ptr(ud),
                                                 _lib.ptr(x), _lib.ptr(F), _lib.ptr(f), _lib.stream_ptr(d))
         _lib.check(rc, "dmpc_mlp_rollout_linearize")
@@ -113,10 +173,10 @@ class MlpDx(torch.nn.Module):
         T = u.shape[0]
         xs, Fs, fs = [x_init], [], []
         for t in range(T - 1):
-            a = self._hidden(xs[t], u[t])
-            nxt = self._output(a, xs[t])
+            z = self._pre(xs[t], u[t])
+            nxt = self._output(_ACT_FN[self.activation][0](z), xs[t])
             if want_model:
-                Fs.append(self._jacobian(a))
+                Fs.append(self._jacobian(z))
                 fs.append(nxt - bmv(Fs[t], torch.cat((xs[t], u[t]), dim=1)))
             xs.append(nxt)
         x = torch.stack(xs, 0)
@@ -147,9 +207,9 @@ class MlpDx(torch.nn.Module):
         xs, Fs, fs = [x0], [], []
         for t in range(T - 1):
             xt, ut = xs[t], u[t]
-            a = self._hidden(xt, ut)
-            nxt = self._output(a, xt)
-            Ft = F_dev[t] if F_dev is not None else self._jacobian(a)
+            z = self._pre(xt, ut)
+            nxt = self._output(_ACT_FN[self.activation][0](z), xt)
+            Ft = F_dev[t] if F_dev is not None else self._jacobian(z)
             Fs.append(Ft)
             fs.append(nxt - bmv(Ft, torch.cat((xt, ut), dim=1)))
             xs.append(nxt)
@@ -191,7 +251,7 @@ class _DeviceLinearize(torch.autograd.Function):
         nbytes = lib.dmpc_mlp_param_grad_workspace_bytes(B, nx, nu, H)
         ws = _workspace(nbytes, d)
         with _lib.guard(d):
-            rc = lib.dmpc_mlp_param_grad(T, B, nx, nu, H, ACT_TANH, int(m.residual), _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2),
+            rc = lib.dmpc_mlp_param_grad(T, B, nx, nu, H, m.act_code, int(m.residual), _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2),
                                          _lib.ptr(b2), _lib.ptr(xs), _lib.ptr(ud), _lib.ptr(g), _lib.ptr(dW1), _lib.ptr(db1),
                                          _lib.ptr(dW2), _lib.ptr(db2), _lib.ptr(dx0), _lib.ptr(du), _lib.ptr(ws), nbytes,
                                          _lib.stream_ptr(d))

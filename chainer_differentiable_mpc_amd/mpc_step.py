@@ -401,8 +401,8 @@ class MPCstep:
             info = torch.zeros(B, dtype=torch.int32, device=d)
             with _lib.guard(d):
                 rc = lib.dmpc_mpc_forward_rec_mlp(
-                    T, B, nx, nu, true_dynamics.n_hidden, 0, int(true_dynamics.residual), _lib.ptr(W1), _lib.ptr(b1),
-                    _lib.ptr(W2), _lib.ptr(b2), _lib.ptr(Kd), _lib.ptr(kd), _lib.ptr(self._u), _lib.ptr(self._xs),
+                    T, B, nx, nu, true_dynamics.n_hidden, true_dynamics.act_code, int(true_dynamics.residual),
+                    _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), _lib.ptr(Kd), _lib.ptr(kd), _lib.ptr(self._u), _lib.ptr(self._xs),
                     _lib.ptr(self._lo), _lib.ptr(self._hi), _lib.ptr(Ct), _lib.ptr(ct), float(ls_decay), int(max_ls_iter),
                     _lib.ptr(x), _lib.ptr(u), _lib.ptr(costs), _lib.ptr(old), _lib.ptr(alphas), _lib.ptr(objs), _lib.ptr(u1),
                     _lib.ptr(nls), _lib.ptr(info), _lib.stream_ptr(d))

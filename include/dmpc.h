@@ -301,15 +301,22 @@ int dmpc_pendulum_rollout_linearize(int T, int B, const float *x_init, const flo
 /* A learned one-hidden-layer dynamics model (MlpDx of the Python layer) as the true dynamics:
  *     next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual != 0)
  * W1 [n_hidden,ns], b1 [n_hidden], W2 [nx,n_hidden], b2 [nx] are DEVICE arrays read by every launch - nothing is cached,
- * an optimiser step in place is seen by the next call.  `act` is a plain int: 0 = tanh, anything else
- * DMPC_E_UNSUPPORTED.  Sizes: nx <= 16, nu <= 8, 1 <= n_hidden <= 256, else DMPC_E_UNSUPPORTED (a NULL pointer or a
+ * an optimiser step in place is seen by the next call.  `act` is a plain int; with z = W1 [x;u] + b1, a = act(z), d = act'(z):
+ *     0  tanh      a = tanh(z)                          d = 1 - a^2
+ *     1  never assigned: DMPC_E_UNSUPPORTED, for good
+ *     2  relu      a = z > 0 ? z : 0 (NaN for a NaN z)  d = z > 0 ? 1 : 0   (0 at z = 0, torch's convention)
+ *     3  silu      a = z s,  s = 1 / (1 + exp(-z))      d = s (1 + z (1 - s))
+ *     4  softplus  a = max(z, 0) + log1p(exp(-|z|))     d = 1 / (1 + exp(-z))
+ * (torch.nn.Softplus at its defaults beta = 1, threshold = 20: beyond the threshold the two differ by less than 2.1e-9,
+ * below float32's resolution there.)  Any other value, negative ones included: DMPC_E_UNSUPPORTED.  The activation selects
+ * a kernel instance at compile time; the tanh instances compute what they computed before the others existed.  Sizes: nx <= 16, nu <= 8, 1 <= n_hidden <= 256, else DMPC_E_UNSUPPORTED (a NULL pointer or a
  * non-positive T, B, nx, nu: DMPC_E_BADARG; both before any HIP call, dmpc_mlp_dx_supported launches nothing); also
  * DMPC_E_UNSUPPORTED where an output array would reach 2^31 elements.  One wavefront per trajectory, the weights in LDS,
- * and ONE step function for both entry points: the states of dmpc_mlp_rollout_linearize and the candidates of the
- * search are bit-equal for equal controls, whatever B is.
+ * and ONE step function per activation for both entry points: the states of dmpc_mlp_rollout_linearize and the
+ * candidates of the search are bit-equal for equal controls, whatever B is.
  *
  * dmpc_mlp_rollout_linearize: get_traj (util.py:239-277) and linearize_dynamics (mpc/approximate.py:77-119, there by
- *   chainer.grad) in one launch: x_0 = x_init, x_{t+1} = next(x_t, u_t), F_t = [I|0] residual + W2 diag(1 - a_t^2) W1,
+ *   chainer.grad) in one launch: x_0 = x_init, x_{t+1} = next(x_t, u_t), F_t = [I|0] residual + W2 diag(d_t) W1,
  *   f_t = x_{t+1} - F_t [x_t;u_t].  x_out [T,B,nx]; F_out [T-1,B,nx,ns] or NULL; f_out [T-1,B,nx] or NULL (NULL with F_out
  *   NULL).  T = 1: x_out = x_init, nothing else is written.
  * dmpc_mpc_forward_rec_mlp: dmpc_mpc_forward_rec (its arguments, outputs, per-trajectory termination, bound snap, test on the
@@ -319,7 +326,7 @@ int dmpc_pendulum_rollout_linearize(int T, int B, const float *x_init, const flo
  *   constant at the value of the live Jacobian (mpc/approximate.py:77-119).  x [T,B,nx] are the states that launch stored,
  *   grad_f [T-1,B,nx] = dL/df (may be NULL when T = 1).  dW1 [n_hidden,ns], db1 [n_hidden], dW2 [nx,n_hidden], db2 [nx] are
  *   WRITTEN (not added to): sum over t and b of r a_t^T, r, delta z_t^T, delta with r = grad_f_t and
- *   delta = (1 - a_t^2) * (W2^T r).  d_x_init [B,nx] and d_u [T,B,nu], each or NULL, are written too: they are exact zeros,
+ *   delta = d_t * (W2^T r).  d_x_init [B,nx] and d_u [T,B,nu], each or NULL, are written too: they are exact zeros,
  *   because the derivative of next through [x_t;u_t] and F_t's cancel at every step.  Two launches: one wavefront walks
  *   trajectories w, w + G, ... (G = dmpc_mlp_param_grad_partials(B) = min(B, 512), a function of B alone) and stores one
  *   partial into ws; the second adds the G partials per element in ascending order.  No atomics: the result is bit-equal

@@ -124,9 +124,10 @@ int main() {
   for (int nx : {0, 1, 3, 16, 17})
     for (int nu : {0, 1, 8, 9})
       for (int H : {0, 1, 5, 64, 256, 257})
-        for (int act : {0, 1})
+        for (int act : {0, 1, 2, 4, 5})
           for (int T : {0, 1, 2, 20}) {
-            const bool sized = nx > 0 && nu > 0, ok = sized && act == 0 && nx <= 16 && nu <= 8 && H >= 1 && H <= 256;
+            const bool act_ok = act == 0 || act == 2 || act == 3 || act == 4;
+            const bool sized = nx > 0 && nu > 0, ok = sized && act_ok && nx <= 16 && nu <= 8 && H >= 1 && H <= 256;
             EXPECT(dmpc_mlp_dx_supported(nx, nu, H, act) == (ok ? 1 : 0));
             const int rr = dmpc_mlp_rollout_linearize(T, 5, nx, nu, H, act, 1, p, p, p, p, p, p, p, p, p, nullptr);
             const int rs = dmpc_mpc_forward_rec_mlp(T, 5, nx, nu, H, act, 1, p, p, p, p, p, p, p, p, p, p, p, p, 0.2f, 10, p, p, p, p,

@@ -9,8 +9,11 @@ kernel launches of one solve of each, and how far the two solutions' costs are a
 `backward` of sum(x) + sum(u), for `MlpDx(device_grad=True)` (the gradient node's backward is `dmpc_mlp_param_grad`) and
 `device_grad=False` (a live torch rollout and autograd through it: the baseline) on equal weights in the same run.
 
+`--activation` picks the network (tanh, relu, silu, softplus; default tanh, whose output lines are what they were before
+the flag existed - another activation adds an "activation" key).
+
     python scripts/mlp_dx_timing.py [--grad] [--iters 20] [--warmup 3] [--cases 3x1x32,8x2x64] [--batch 128] [--horizon 20]
-                                    [--json out]"""
+                                    [--activation tanh] [--json out]"""
 import argparse
 import json
 import os
@@ -53,12 +56,14 @@ def count_launches(fn):
         return None
 
 
-def run_case(nx, nu, H, B, T, iters, warmup):
+def run_case(nx, nu, H, B, T, iters, warmup, activation="tanh"):
     p = synthetic.make_lqr_problem(B, T, nx, nu, seed=1)
     dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device="cuda")   # noqa: E731
     x0, cost = dev(p["x_init"]), QuadCost(dev(p["C"]), dev(p["c"]))
-    m = MlpDx(nx, nu, H, seed=0).cuda()
+    m = MlpDx(nx, nu, H, seed=0, activation=activation).cuda()
     out = dict(nx=nx, nu=nu, n_hidden=H, B=B, T=T)
+    if activation != "tanh":
+        out["activation"] = activation
     sols = {}
     for tag, dyn in (("device", m), ("callable", lambda x, u: m(x, u))):
         solver = BoxDDP(T, -0.5, 0.5, B, nx, nu, None, max_iter=10, quiet=True)
@@ -76,7 +81,7 @@ def run_case(nx, nu, H, B, T, iters, warmup):
     return out
 
 
-def run_grad_case(nx, nu, H, B, T, iters, warmup):
+def run_grad_case(nx, nu, H, B, T, iters, warmup, activation="tanh"):
     """both routes on equal weights, alternating solve by solve; per route the median of solve + backward and of the
     backward alone (device events, host time included), the launches of one solve + backward, the sampled clocks"""
     from bench import ClockSampler
@@ -84,9 +89,11 @@ def run_grad_case(nx, nu, H, B, T, iters, warmup):
     dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device="cuda")   # noqa: E731
     x0, cost = dev(p["x_init"]), QuadCost(dev(p["C"]), dev(p["c"]))
     out = dict(nx=nx, nu=nu, n_hidden=H, B=B, T=T, leg="grad", rounds=iters)
+    if activation != "tanh":
+        out["activation"] = activation
     routes = {}
     for tag, flag in (("device_grad", True), ("live", False)):
-        m = MlpDx(nx, nu, H, seed=0, device_grad=flag).cuda()
+        m = MlpDx(nx, nu, H, seed=0, device_grad=flag, activation=activation).cuda()
         solver = BoxDDP(T, -0.5, 0.5, B, nx, nu, None, max_iter=10, quiet=True, update_dynamics=True, detach_unconverged=False)
         routes[tag] = (m, solver, [], [])
 
@@ -135,12 +142,13 @@ def main():
     ap.add_argument("--cases", default="3x1x32,8x2x64")
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--horizon", type=int, default=20)
+    ap.add_argument("--activation", default="tanh", choices=["tanh", "relu", "silu", "softplus"])
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     res = []
     for c in a.cases.split(","):
         nx, nu, H = (int(v) for v in c.split("x"))
-        r = (run_grad_case if a.grad else run_case)(nx, nu, H, a.batch, a.horizon, max(a.iters, 20), a.warmup)
+        r = (run_grad_case if a.grad else run_case)(nx, nu, H, a.batch, a.horizon, max(a.iters, 20), a.warmup, a.activation)
         print(json.dumps(r), flush=True)
         res.append(r)
     if a.json:
