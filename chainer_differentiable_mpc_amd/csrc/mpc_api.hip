@@ -113,6 +113,15 @@ static int launch_fixed_grid(const void *kernel, int rows, void **args, hipStrea
   return DMPC_E_UNSUPPORTED;
 }
 
+// A batch-coupled problem on a register kernel: cooperative, the whole batch resident; where that does not fit - and with
+// DMPC_NO_COOP_REGISTER=1, read at every call - what `fixed_grid` launches instead (mpc_coupled.hpp)
+template <class FixedGrid>
+static int launch_coupled(const void *kernel, dim3 grid, dim3 block, void **args, size_t lds, hipStream_t stream, FixedGrid fixed_grid) {
+  const int rc = knob_on_now<Knob::DMPC_NO_COOP_REGISTER>() ? DMPC_E_UNSUPPORTED
+                                                            : launch_cooperative(kernel, grid, block, args, lds, stream);
+  return rc == DMPC_E_UNSUPPORTED ? fixed_grid() : rc;
+}
+
 static size_t coupled_bytes(int T, int n_qp_iter) { return round_up((size_t)T * pnqp_sync_slots(n_qp_iter) * 2 * sizeof(unsigned), 256); }
 // the fixed-grid form's rows, behind the decision slots
 static size_t coupled_traj_bytes(int B, int nx, int nu) { return round_up((size_t)B * mpc_coupled_traj_floats(nx, nu) * sizeof(float), 256); }
@@ -129,6 +138,7 @@ static int launch_mpc_back_fixed_grid(int nx, int nu, const MpcBackArgs &a, hipS
   return launch_fixed_grid(reinterpret_cast<const void *>(&mpc_coupled_backward_kernel), a.B, args, stream);
 }
 
+// ---- The instance lists, in the order they are tried.
 #ifdef DMPC_EXPERIMENT_ONLY_8_2
 #define DMPC_MPC_SHAPES(X) X(8, 2, 16)
 #else
@@ -136,7 +146,9 @@ static int launch_mpc_back_fixed_grid(int nx, int nu, const MpcBackArgs &a, hipS
   X(1, 1, 16) X(2, 1, 16) X(3, 1, 16) X(2, 2, 16) X(3, 2, 16) X(4, 2, 16) X(6, 2, 16) X(8, 2, 16) \
   X(4, 4, 16) X(8, 4, 16) X(12, 3, 16)
 #endif
-
+// The generated streams (mpc_asm_kernel.hpp, mpc_fwd_asm_kernel.hpp, mpc_step_fused_kernel.hpp); (6,2) has a search alone
+#define DMPC_MPC_STREAM_SHAPES(A, SEARCH_ONLY) A(8, 2) A(3, 1) A(4, 2) SEARCH_ONLY(6, 2) A(2, 2) A(1, 1) A(2, 1) A(3, 2)
+#define DMPC_NO_SHAPE(NX_, NU_)
 // Containers (mpc_backward_rec_kernel / mpc_forward_rec_kernel <..., PAD>): any smaller problem runs padded inside them
 // instead of on the runtime-dimension kernels of mpc_generic.hpp; tried in this order (same list as lqr_api.hip)
 #ifdef DMPC_EXPERIMENT_ONLY_8_2
@@ -144,6 +156,80 @@ static int launch_mpc_back_fixed_grid(int nx, int nu, const MpcBackArgs &a, hipS
 #else
 #define DMPC_MPC_CONTAINERS(X) X(3, 1) X(4, 4) X(8, 2) X(8, 4) X(14, 1) X(13, 2) X(12, 3) X(11, 4)
 #endif
+// The wide row kernels' instances (lqr_wide_kernel<..., MPC>, mpc_wide_forward_kernel), fewest columns first
+#define DMPC_MPC_WIDE_SHAPES(X) X(12, 4) X(16, 4) X(12, 8) X(16, 8)
+// pnqp_kernel<N> and mpc_generic_backward_kernel<NU>: up to eight unknowns / controls (kMpcGenericMaxNu)
+#define DMPC_ONE_TO_EIGHT(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8)
+
+// The LDS-DMA rings of the 16-lane kernels' inputs (mpc_dma_kernels.hpp): the sweep's depth by the DMA instructions a step takes
+template <int NX, int NU>
+struct SweepRing {
+  static constexpr int kDma = MpcBackDmaLayout<NX, NU, 2>::kDma, kDepth = kDma == 1 ? 8 : kDma <= 4 ? 4 : 2;
+  static constexpr size_t kLds = MpcBackDmaLayout<NX, NU, kDepth>::lds_bytes();
+  static constexpr bool kFits = kLds <= 65536;
+};
+template <int NX, int NU>
+constexpr bool search_ring_fits() { return MpcFwdDmaLayout<NX, NU>::lds_bytes() <= 96 * 1024; }
+
+// ---- The order of the code object.  The compiler emits the kernels in the order the translation unit first names them
+// (DESIGN.md 3.4); the launchers below would name them in another.  This function names every kernel template instance of the
+// family in the order the code object has had; nothing calls it.
+template <class... K>
+static void name_kernels(K...) {}
+[[maybe_unused]] static void kernel_order() {
+#define A(NX_, NU_)                                                                                                       \
+  name_kernels(mpc_backward_asm_select_kernel<NX_, NU_, false, true>, mpc_backward_asm_kernel<NX_, NU_, false, true>,     \
+               mpc_backward_asm_select_kernel<NX_, NU_, true, false>, mpc_backward_asm_kernel<NX_, NU_, true, false>,     \
+               mpc_backward_asm_select_kernel<NX_, NU_, false, false>, mpc_backward_asm_kernel<NX_, NU_, false, false>);
+  DMPC_MPC_STREAM_SHAPES(A, DMPC_NO_SHAPE)
+#undef A
+#define X(NX_, NU_, L_)                                                                                                   \
+  if constexpr (L_ == 16 && SweepRing<NX_, NU_>::kFits)                                                                   \
+    name_kernels(mpc_backward_rec_dma_select_kernel<NX_, NU_, SweepRing<NX_, NU_>::kDepth>,                               \
+                 mpc_backward_rec_dma_kernel<NX_, NU_, SweepRing<NX_, NU_>::kDepth>);                                     \
+  name_kernels(mpc_backward_rec_kernel<NX_, NU_, L_, false>);
+  DMPC_MPC_SHAPES(X)
+#undef X
+#define X(NX_, NU_) name_kernels(lqr_wide_kernel<NX_, NU_, 2, 2, false, false, true>);
+  DMPC_MPC_WIDE_SHAPES(X)
+#undef X
+#define X(NX_, NU_) name_kernels(lqr_wide_kernel<NX_, NU_, 2, 2, true, false, true>);
+  DMPC_MPC_WIDE_SHAPES(X)
+#undef X
+#define X(NX_, NU_) name_kernels(mpc_backward_rec_kernel<NX_, NU_, 16, true>);
+  DMPC_MPC_CONTAINERS(X)
+#undef X
+#define X(NU_) name_kernels(mpc_generic_backward_kernel<NU_>);
+  DMPC_ONE_TO_EIGHT(X)
+#undef X
+  name_kernels(mpc_forward_rec_pendulum_spec_kernel<true>, mpc_forward_rec_pendulum_spec_kernel<false>);
+#define A(NX_, NU_) name_kernels(mpc_forward_asm_kernel<NX_, NU_>);
+  DMPC_MPC_STREAM_SHAPES(A, A)
+#undef A
+#define X(NX_, NU_, L_)                                                                                                   \
+  if constexpr (L_ == 16 && search_ring_fits<NX_, NU_>()) name_kernels(mpc_forward_rec_kernel<NX_, NU_, L_, true, false>); \
+  name_kernels(mpc_forward_rec_kernel<NX_, NU_, L_, false, false>);
+  DMPC_MPC_SHAPES(X)
+#undef X
+#define X(NX_, NU_) name_kernels(mpc_wide_forward_kernel<NX_, NU_, 2, false>);
+  DMPC_MPC_WIDE_SHAPES(X)
+#undef X
+#define X(NX_, NU_) name_kernels(mpc_wide_forward_kernel<NX_, NU_, 2, true>);
+  DMPC_MPC_WIDE_SHAPES(X)
+#undef X
+#define X(NX_, NU_) name_kernels(mpc_forward_rec_kernel<NX_, NU_, 16, false, true>);
+  DMPC_MPC_CONTAINERS(X)
+#undef X
+#define A(NX_, NU_)                                                                                                       \
+  name_kernels(mpc_step_fused_asm_kernel<NX_, NU_, false, true>, mpc_step_fused_asm_kernel<NX_, NU_, true, false>,        \
+               mpc_step_fused_asm_kernel<NX_, NU_, false, false>);
+  DMPC_MPC_STREAM_SHAPES(A, DMPC_NO_SHAPE)
+#undef A
+#define X(N_) name_kernels(pnqp_kernel<N_>);
+  DMPC_ONE_TO_EIGHT(X)
+#undef X
+}
+
 // Which shapes run padded inside the wide row kernels' instances (sweep and line search alike): those without a 16-lane MPC
 // container (16 and more elements of tau, or more than four controls) and, of those with one, three and four controls from
 // 12 elements on - MPCstep.forward at B = 4096, T = 50: (9,4) 707 -> 605 us, (11,4) 769 -> 645, (10,3) 629 -> 578; with one
@@ -158,216 +244,155 @@ static bool aligned16(const P *...p) {   // nullptr counts as aligned
 // workgroups that share the bookkeeping of one box-DDP iteration inside the fused sweep launch: 256 rows each
 static int select_parts(int B) { const int n = (B + 255) / 256; return n < 1 ? 1 : (n > 8 ? 8 : n); }
 
-// can launch_mpc_back stage this problem's inputs through the LDS-DMA ring?
-static bool mpc_back_dma_ok(const MpcBackArgs &a) {
-  return a.sync == nullptr && a.B >= 4 && a.B % 4 == 0 && !knob_on<Knob::DMPC_NO_MPC_DMA>() &&
-         aligned16(a.C, a.c, a.F, a.f, a.controls, a.lower, a.upper, a.states);
+// ---- The launchers: one per kernel template.  A job is the entry point's arguments and the problem's own dimensions; the
+// launcher of a container tells its kernel the dimensions on a copy, so the caller's arguments stay as they are.
+struct MpcSweepJob {
+  const MpcBackArgs &a;
+  int nx, nu;
+  // BoxDDP's fused chain: further workgroups of the (3,1) stream and ring kernels run box_ddp_select_body(*sel), the
+  // bookkeeping of the iteration before; nullptr otherwise
+  const DdpSelectArgs *sel;
+  unsigned *sel_sync;
+};
+struct MpcSearchJob {
+  const MpcFwdArgs &a;
+  int nx, nu;
+};
+using MpcSweepLauncher = int (*)(const MpcSweepJob &j, hipStream_t stream);
+using MpcSearchLauncher = int (*)(const MpcSearchJob &j, hipStream_t stream);
+using MpcStepLauncher = int (*)(const MpcBackArgs &ba, const MpcFwdArgs &fa, hipStream_t stream);
+// a copy of the arguments that tells a padded kernel the problem's dimensions (`pad` false: the copy alone)
+template <class Args>
+static Args told_dims(Args a, bool pad, int nx, int nu) {
+  a.nx_log = pad ? nx : a.nx_log;
+  a.nu_log = pad ? nu : a.nu_log;
+  return a;
 }
 
-// sel != nullptr (nx = 3, nu = 1 and mpc_back_dma_ok only): one more workgroup runs box_ddp_select_body(*sel)
-static int launch_mpc_back(int nx, int nu, const MpcBackArgs &a_in, hipStream_t stream, const DdpSelectArgs *sel = nullptr,
-                           unsigned *sel_sync = nullptr) {
-  MpcBackArgs a = a_in;
-  if (a.sync != nullptr) {   // fresh decision slots for this launch
-    const hipError_t e = hipMemsetAsync(a.sync, 0, coupled_bytes(a.T, a.n_qp_iter), stream);
-    if (e != hipSuccess) return (int)e;
-  }
-  void *args1[] = {&a};
-  // DMPC_NO_COOP_REGISTER=1: batch-coupled problems skip the register kernels' whole-batch-resident launch and run on
-  // mpc_coupled.hpp's fixed grid, as they do when that launch does not fit
-  const bool coop_off = a.sync != nullptr && knob_on_now<Knob::DMPC_NO_COOP_REGISTER>();
-  // per-trajectory termination, whole wavefronts of four trajectories, 16-byte aligned runs: inputs through the LDS-DMA
-  // ring of mpc_dma_kernels.hpp (DMPC_NO_MPC_DMA=1: the register-bank kernel, for A/B timing)
-  const bool dma_ok = mpc_back_dma_ok(a);
-  // The sweep as one generated instruction stream with the box QP inside (mpc_asm_kernel.hpp): shapes the generator
-  // covers, c already re-centred, no bookkeeping riding along.  DMPC_NO_MPC_ASM=1: the HIP kernels (A/B timing).
-  if (dma_ok && a.T >= 2 && !knob_on<Knob::DMPC_NO_MPC_ASM>() && (sel == nullptr || sel_sync != nullptr) &&
-      (a.states == nullptr || a.f == nullptr)) {
-    const int n_sel = sel != nullptr ? select_parts(a.B) : 0;
-    const dim3 grid((a.B + 15) / 16 + n_sel), block(256);
-    const int variant = a.states != nullptr ? 2 : (a.f != nullptr ? 1 : 0);   // re-centring / with f_hat / plain
-#define L_(K_, ...)                                                                                            \
-  if (sel != nullptr) DMPC_LAUNCH_GGL((mpc_backward_asm_select_kernel<__VA_ARGS__>), grid, block, K_, stream, a, *sel, n_sel, sel_sync); \
-  else DMPC_LAUNCH_GGL((mpc_backward_asm_kernel<__VA_ARGS__>), grid, block, K_, stream, a);
-#define A(NX_, NU_)                                                                                            \
-  if (nx == NX_ && nu == NU_) {                                                                                \
-    constexpr size_t lds = mpc_asm_lds_bytes<NX_, NU_>();                                                      \
-    if (variant == 2) { L_(lds, NX_, NU_, false, true) }                                                       \
-    else if (variant == 1) { L_(lds, NX_, NU_, true, false) }                                                  \
-    else { L_(lds, NX_, NU_, false, false) }                                                                   \
-    return (int)hipGetLastError();                                                                             \
-  }
-    A(8, 2) A(3, 1) A(4, 2) A(2, 2) A(1, 1) A(2, 1) A(3, 2)
-#undef A
-#undef L_
-  }
-#define X(NX_, NU_, L_)                                                                                       \
-  if (nx == NX_ && nu == NU_) {                                                                               \
-    constexpr int GPB = 256 / L_;                                                                             \
-    if constexpr (L_ == 16) {                                                                                 \
-      constexpr int kD = MpcBackDmaLayout<NX_, NU_, 2>::kDma, DB_ = kD == 1 ? 8 : kD <= 4 ? 4 : 2;            \
-      if constexpr (MpcBackDmaLayout<NX_, NU_, DB_>::lds_bytes() <= 65536) {                                  \
-        if (dma_ok && sel != nullptr) {                                                                       \
-          const int n_sel = select_parts(a.B);                                                                \
-          DMPC_LAUNCH_GGL((mpc_backward_rec_dma_select_kernel<NX_, NU_, DB_>), dim3((a.B + 15) / 16 + n_sel), \
-                             dim3(256), (MpcBackDmaLayout<NX_, NU_, DB_>::lds_bytes()), stream, a, *sel, n_sel, \
-                             sel_sync);                                                                       \
-          return (int)hipGetLastError();                                                                      \
-        }                                                                                                     \
-        if (dma_ok) {                                                                                         \
-          DMPC_LAUNCH_GGL((mpc_backward_rec_dma_kernel<NX_, NU_, DB_>), dim3((a.B + 15) / 16), dim3(256),  \
-                             (MpcBackDmaLayout<NX_, NU_, DB_>::lds_bytes()), stream, a);                      \
-          return (int)hipGetLastError();                                                                      \
-        }                                                                                                     \
-      }                                                                                                       \
-    }                                                                                                         \
-    if (a.sync != nullptr) {                                                                                  \
-      const int rc = coop_off ? DMPC_E_UNSUPPORTED                                                            \
-                              : launch_cooperative(reinterpret_cast<const void *>(&mpc_backward_rec_kernel<NX_, NU_, L_>), \
-                                                   dim3((a.B + GPB - 1) / GPB), dim3(256), args1, 0, stream); \
-      return rc == DMPC_E_UNSUPPORTED ? launch_mpc_back_fixed_grid(nx, nu, a, stream) : rc;                   \
-    }                                                                                                         \
-    DMPC_LAUNCH_GGL((mpc_backward_rec_kernel<NX_, NU_, L_>), dim3((a.B + GPB - 1) / GPB), dim3(256), 0, stream, \
-                       a);                                                                                    \
-    return (int)hipGetLastError();                                                                            \
-  }
-  if (sel != nullptr && !(dma_ok && sel_sync != nullptr)) return DMPC_E_BADARG;   // callers ask mpc_back_dma_ok first
-  DMPC_MPC_SHAPES(X)
-#undef X
-  // (12,4), (16,4), (12,8), (16,8): the sweep on the wide row kernel with the box QP inside (lqr_wide_kernel<..., MPC>: four
-  // trajectories per wavefront, matrix-core products; before, the runtime-dimension kernel - 2.0 ms at (12,4), B = 4096, T = 50 -
-  // and, at (16,8), a wavefront per trajectory).  DMPC_NO_WIDE=1: those.
-  {
-    if (!knob_on<Knob::DMPC_NO_WIDE>() && a.sync == nullptr && sel == nullptr && a.B >= 4 && a.T >= 2 &&
-        aligned16(a.C, a.c, a.F, a.f) && (size_t)a.B * (nx + nu) * (nx + nu) * 4 < ((size_t)1 << 31)) {
-      LqrArgs s{a.T, a.B, a.C, a.c, a.F, a.f, nullptr, nullptr, a.Ks, a.ks, nullptr, nullptr, nullptr, nullptr, a.info};
-      s.mpc_controls = a.controls;
-      s.mpc_lower = a.lower;
-      s.mpc_upper = a.upper;
-      s.mpc_states = a.states;
-      s.mpc_n_qp_iter = a.n_qp_iter;
-      s.mpc_n_qp_total = a.n_qp_total;
-      s.mpc_done = a.done;
-      s.info_store = a.info_store != 0;
-#define X(NX_, NU_)                                                                                            \
-  if (nx == NX_ && nu == NU_) {                                                                                \
-    constexpr size_t lds = LqrWideLayout<NX_, NU_, 2, 2>::lds_bytes();                                         \
-    if (lds > 64 * 1024)                                                                                       \
-      set_max_lds(reinterpret_cast<const void *>(&lqr_wide_kernel<NX_, NU_, 2, 2, false, false, true>), \
-                                (int)lds);                         \
-    DMPC_LAUNCH_GGL((lqr_wide_kernel<NX_, NU_, 2, 2, false, false, true>), dim3((s.B + 15) / 16), dim3(256), lds, stream, s); \
-    return (int)hipGetLastError();                                                                             \
-  }
-      X(12, 4) X(16, 4) X(12, 8) X(16, 8)
-#undef X
-      // ... and padded inside the smallest of those instances: every other shape with at most 16 states, 8 controls and
-      // no 16-lane container (nx + nu >= 16, or more than four controls: (5,5) 2.0 -> 1.3 ms per MPCstep.forward), whole wavefronts
-      if (nx >= 1 && nu >= 1 && nx <= 16 && nu <= 8 && mpc_wide_padded(nx, nu) && a.B % 4 == 0 &&
-          !knob_on<Knob::DMPC_NO_CONTAINER>()) {
-        s.nx_log = nx;
-        s.nu_log = nu;
-#define X(NX_, NU_)                                                                                            \
-  if (nx <= NX_ && nu <= NU_) {                                                                                \
-    constexpr size_t lds = LqrWideLayout<NX_, NU_, 2, 2>::lds_bytes();                                         \
-    if (lds > 64 * 1024)                                                                                       \
-      set_max_lds(reinterpret_cast<const void *>(&lqr_wide_kernel<NX_, NU_, 2, 2, true, false, true>), \
-                                (int)lds);                         \
-    DMPC_LAUNCH_GGL((lqr_wide_kernel<NX_, NU_, 2, 2, true, false, true>), dim3((s.B + 15) / 16), dim3(256), lds, stream, s); \
-    return (int)hipGetLastError();                                                                             \
-  }
-        X(12, 4) X(16, 4) X(12, 8) X(16, 8)
-#undef X
-      }
-    }
-  }
-  // (16,8), (32,8): the matrix-core sweep with the box QP inside (lqr_wave_mfma_backward<..., MPC>); per-trajectory
-  // termination, not inside the device-driven BoxDDP loop (no `done` flag there)
-  if (a.sync == nullptr && a.done == nullptr && !a.info_store && ((nx == 16 && nu == 8) || (nx == 32 && nu == 8)) &&
-      a.T >= 1 && !knob_on<Knob::DMPC_NO_MPC_WAVE>()) {
-    LqrArgs s{a.T, a.B, a.C, a.c, a.F, a.f, nullptr, nullptr, a.Ks, a.ks, nullptr, nullptr, nullptr, nullptr, a.info};
-    s.mpc_controls = a.controls;
-    s.mpc_lower = a.lower;
-    s.mpc_upper = a.upper;
-    s.mpc_states = a.states;
-    s.mpc_n_qp_iter = a.n_qp_iter;
-    s.mpc_n_qp_total = a.n_qp_total;
-    return launch_mpc_wave_backward(nx, nu, s, stream);
-  }
-  auto wave_container = [&](int cnx, int cnu) {   // wider than the 16-lane containers: padded inside a wave instance
-    LqrArgs s{a.T, a.B, a.C, a.c, a.F, a.f, nullptr, nullptr, a.Ks, a.ks, nullptr, nullptr, nullptr, nullptr, a.info};
-    s.mpc_controls = a.controls;
-    s.mpc_lower = a.lower;
-    s.mpc_upper = a.upper;
-    s.mpc_states = a.states;
-    s.mpc_n_qp_iter = a.n_qp_iter;
-    s.mpc_n_qp_total = a.n_qp_total;
-    s.nx_log = nx;
-    s.nu_log = nu;
-    return launch_mpc_wave_container_backward(cnx, cnu, s, stream);
-  };
-  const bool wave_ok = a.sync == nullptr && a.done == nullptr && !a.info_store && !knob_on<Knob::DMPC_NO_MPC_WAVE>() &&
-                       !knob_on<Knob::DMPC_NO_CONTAINER>();
-  const bool small = nu <= 4 && nx + nu <= 15;     // (the 16-lane containers below take these)
-  if (!knob_on<Knob::DMPC_NO_CONTAINER>()) {   // a smaller problem inside the first container that holds it
-    a.nx_log = nx;
-    a.nu_log = nu;
-#define X(NX_, NU_)                                                                                           \
-  if (nx <= NX_ && nu <= NU_) {                                                                               \
-    if (a.sync != nullptr) {                                                                                  \
-      const int rc = coop_off ? DMPC_E_UNSUPPORTED                                                            \
-                              : launch_cooperative(reinterpret_cast<const void *>(&mpc_backward_rec_kernel<NX_, NU_, 16, true>), \
-                                                   dim3((a.B + 15) / 16), dim3(256), args1, 0, stream);       \
-      a.nx_log = a.nu_log = 0;                                                                                \
-      return rc == DMPC_E_UNSUPPORTED ? launch_mpc_back_fixed_grid(nx, nu, a, stream) : rc;                   \
-    }                                                                                                         \
-    DMPC_LAUNCH_GGL((mpc_backward_rec_kernel<NX_, NU_, 16, true>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a); \
-    return (int)hipGetLastError();                                                                            \
-  }
-    DMPC_MPC_CONTAINERS(X)
-#undef X
-  }
-  // A padded wave instance costs what ITS shape costs (and fetches element by element, one wavefront per SIMD): measured at
-  // B = 4096, T = 50 it beats the runtime-dimension kernel where the latter's QP in lane 0 is widest - (24,8) 9.2 against
-  // 12.5 ms - and lost below - (20,6) 7.8 against 5.4 ms, (10,5) 5.4 against 2.9 ms.
-  // (Round 4, the padded instance fetching through its LDS-DMA slot: (20,6) 3.4 against 3.8 ms - six controls and more.)
-  // (Round 5, from 21 states on with three to five controls, from 24 with one or two: the runtime-dimension kernel's cost grows with nx^2 in one lane group -
-  // (32,4) 7.7 ms, (32,2) 6.4, (23,4) 4.2, (24,4) 3.9 - where the padded (32,8) instance stays at ~3 ms: (32,4) 3.1, (32,2) 2.8, (24,4) 3.0.)
-  if (wave_ok && !small && nu >= 6 && nx <= 16 && nu <= 8) return wave_container(16, 8);
-  if (wave_ok && !small && (nu >= 6 || nx >= (nu >= 3 ? 21 : 24)) && nx <= 32 && nu <= 8) return wave_container(32, 8);
-  // any other shape with nx + nu + 1 <= 64, nu <= 8: runtime-dimension kernel (mpc_generic.hpp)
-  if (nx + nu + 1 <= 64 && nu <= kMpcGenericMaxNu) {
-    void *args2[] = {&a, &nx};
-#define G(NU_)                                                                                                    \
-  case NU_:                                                                                                       \
-    if (a.sync != nullptr) {                                                                                      \
-      const int rc = coop_off ? DMPC_E_UNSUPPORTED                                                                \
-                              : launch_cooperative(reinterpret_cast<const void *>(&mpc_generic_backward_kernel<NU_>), dim3(a.B), \
-                                                   dim3(64), args2, mpc_generic_back_lds_bytes<NU_>(nx), stream); \
-      return rc == DMPC_E_UNSUPPORTED ? launch_mpc_back_fixed_grid(nx, nu, a, stream) : rc;                       \
-    }                                                                                                             \
-    DMPC_LAUNCH_GGL((mpc_generic_backward_kernel<NU_>), dim3(a.B), dim3(64), mpc_generic_back_lds_bytes<NU_>(nx), \
-                       stream, a, nx);                                                                            \
-    return (int)hipGetLastError();
-    switch (nu) { G(1) G(2) G(3) G(4) G(5) G(6) G(7) G(8) }
-#undef G
-  }
-  // any other size (more than 8 controls, more than 64 columns): a workgroup per trajectory, matrices in the caller's
-  // workspace (mpc_tiled.hpp; batch-coupled: mpc_coupled.hpp)
-  if (a.sync != nullptr) {
-    a.nx_log = a.nu_log = 0;
-    return launch_mpc_back_fixed_grid(nx, nu, a, stream);
-  }
-  if (a.tiled_scratch != nullptr) {
-    const size_t shmem = (pnqp_tiled_lds_floats(nu) + (size_t)(nx + nu)) * sizeof(float);
-    if (shmem > 60 * 1024) return DMPC_E_UNSUPPORTED;
-    DMPC_LAUNCH_GGL(mpc_tiled_backward_kernel, dim3(a.B), dim3(kTiledThreads), shmem, stream, a, nx, nu, a.tiled_scratch);
-    return (int)hipGetLastError();
-  }
-  return DMPC_E_WORKSPACE;
+// the three forms of the generated sweep: c as given / with f_hat / c re-centred around `states` inside the sweep
+template <class F>
+static int with_sweep_form(const MpcBackArgs &a, F f) {
+  return with_bools([&](auto has_f, auto recentre) -> int {
+    if constexpr (decltype(has_f)::value && decltype(recentre)::value) return DMPC_E_UNSUPPORTED;   // (no such stream, no such call)
+    else return f(has_f, recentre);
+  }, a.states == nullptr && a.f != nullptr, a.states != nullptr);
 }
 
-// shapes that only the tiled kernels take
-static bool mpc_needs_tiles(int nx, int nu) { return !(nx + nu + 1 <= 64 && nu <= kMpcGenericMaxNu); }
+// The sweep as one generated instruction stream with the box QP inside (mpc_asm_kernel.hpp)
+template <int NX, int NU>
+static int launch_sweep_stream(const MpcSweepJob &j, hipStream_t stream) {
+  const int n_sel = j.sel != nullptr ? select_parts(j.a.B) : 0;
+  const dim3 grid((j.a.B + 15) / 16 + n_sel), block(256);
+  constexpr size_t lds = mpc_asm_lds_bytes<NX, NU>();
+  return with_sweep_form(j.a, [&](auto has_f, auto recentre) {
+    constexpr bool F = decltype(has_f)::value, R = decltype(recentre)::value;
+    return with_bools([&](auto select) {
+      if constexpr (decltype(select)::value)
+        return launch_kernel(mpc_backward_asm_select_kernel<NX, NU, F, R>, grid, block, lds, stream, j.a, *j.sel, n_sel, j.sel_sync);
+      else
+        return launch_kernel(mpc_backward_asm_kernel<NX, NU, F, R>, grid, block, lds, stream, j.a);
+    }, j.sel != nullptr);
+  });
+}
+
+// Inputs through the LDS-DMA ring of mpc_dma_kernels.hpp
+template <int NX, int NU>
+static int launch_sweep_ring(const MpcSweepJob &j, hipStream_t stream) {
+  using Ring = SweepRing<NX, NU>;
+  const int n_sel = j.sel != nullptr ? select_parts(j.a.B) : 0;
+  const dim3 grid((j.a.B + 15) / 16 + n_sel), block(256);
+  return with_bools([&](auto select) {
+    if constexpr (decltype(select)::value)
+      return launch_kernel(mpc_backward_rec_dma_select_kernel<NX, NU, Ring::kDepth>, grid, block, Ring::kLds, stream, j.a, *j.sel,
+                           n_sel, j.sel_sync);
+    else
+      return launch_kernel(mpc_backward_rec_dma_kernel<NX, NU, Ring::kDepth>, grid, block, Ring::kLds, stream, j.a);
+  }, j.sel != nullptr);
+}
+
+static int launch_sweep_fixed_grid(const MpcSweepJob &j, hipStream_t stream) { return launch_mpc_back_fixed_grid(j.nx, j.nu, j.a, stream); }
+// (batch-coupled: `a` is the launcher's copy that `args` point to)
+static int launch_sweep_coupled(const void *kernel, dim3 grid, dim3 block, void **args, size_t lds, const MpcSweepJob &j,
+                                hipStream_t stream) {
+  return launch_coupled(kernel, grid, block, args, lds, stream, [&] { return launch_sweep_fixed_grid(j, stream); });
+}
+
+// mpc_backward_rec_kernel: a lane group per trajectory, inputs through register banks.  PAD: a container
+template <int NX, int NU, int L, bool PAD>
+static int launch_sweep_rows(const MpcSweepJob &j, hipStream_t stream) {
+  constexpr int GPB = 256 / L;
+  MpcBackArgs a = told_dims(j.a, PAD, j.nx, j.nu);
+  const dim3 grid((a.B + GPB - 1) / GPB), block(256);
+  if (a.sync == nullptr) return launch_kernel(mpc_backward_rec_kernel<NX, NU, L, PAD>, grid, block, 0, stream, a);
+  void *args[] = {&a};
+  return launch_sweep_coupled(reinterpret_cast<const void *>(&mpc_backward_rec_kernel<NX, NU, L, PAD>), grid, block, args, 0, j, stream);
+}
+
+// the sweeps of lqr_wide_kernel.hpp and lqr_wave_api.hip take the box QP's arguments inside an LqrArgs
+static LqrArgs as_lqr_args(const MpcBackArgs &a) {
+  LqrArgs s{a.T, a.B, a.C, a.c, a.F, a.f, nullptr, nullptr, a.Ks, a.ks, nullptr, nullptr, nullptr, nullptr, a.info};
+  s.mpc_controls = a.controls;
+  s.mpc_lower = a.lower;
+  s.mpc_upper = a.upper;
+  s.mpc_states = a.states;
+  s.mpc_n_qp_iter = a.n_qp_iter;
+  s.mpc_n_qp_total = a.n_qp_total;
+  s.mpc_done = a.done;
+  s.info_store = a.info_store != 0;
+  return s;
+}
+
+// (12,4), (16,4), (12,8), (16,8): the sweep on the wide row kernel with the box QP inside (lqr_wide_kernel<..., MPC>: four
+// trajectories per wavefront, matrix-core products; before, the runtime-dimension kernel - 2.0 ms at (12,4), B = 4096, T = 50 -
+// and, at (16,8), a wavefront per trajectory) - and, padded inside the smallest of those instances, every other shape of
+// mpc_wide_padded ((5,5): 2.0 -> 1.3 ms per MPCstep.forward)
+template <int NX, int NU>
+static int launch_sweep_wide(const MpcSweepJob &j, hipStream_t stream) {
+  const bool pad = j.nx != NX || j.nu != NU;
+  const LqrArgs s = told_dims(as_lqr_args(j.a), pad, j.nx, j.nu);
+  return with_bools([&](auto PAD) {
+    return launch_kernel_big_lds(lqr_wide_kernel<NX, NU, 2, 2, decltype(PAD)::value, false, true>, dim3((s.B + 15) / 16), dim3(256),
+                                 LqrWideLayout<NX, NU, 2, 2>::lds_bytes(), stream, s);
+  }, pad);
+}
+
+// (16,8), (32,8): the matrix-core sweep with the box QP inside (lqr_wave_mfma_backward<..., MPC>) ...
+static int launch_sweep_wave(const MpcSweepJob &j, hipStream_t stream) {
+  return launch_mpc_wave_backward(j.nx, j.nu, as_lqr_args(j.a), stream);
+}
+// ... and a problem wider than the 16-lane containers padded inside one of those instances
+template <int NX, int NU>
+static int launch_sweep_wave_container(const MpcSweepJob &j, hipStream_t stream) {
+  return launch_mpc_wave_container_backward(NX, NU, told_dims(as_lqr_args(j.a), true, j.nx, j.nu), stream);
+}
+
+// the runtime-dimension kernel (mpc_generic.hpp)
+template <int NU>
+static int launch_sweep_generic(const MpcSweepJob &j, hipStream_t stream) {
+  const size_t lds = mpc_generic_back_lds_bytes<NU>(j.nx);
+  const dim3 grid(j.a.B), block(64);
+  if (j.a.sync == nullptr) return launch_kernel(mpc_generic_backward_kernel<NU>, grid, block, lds, stream, j.a, j.nx);
+  MpcBackArgs a = j.a;
+  int nx = j.nx;
+  void *args[] = {&a, &nx};
+  return launch_sweep_coupled(reinterpret_cast<const void *>(&mpc_generic_backward_kernel<NU>), grid, block, args, lds, j, stream);
+}
+
+// a workgroup per trajectory, matrices in the caller's workspace (mpc_tiled.hpp)
+static size_t sweep_tiled_lds_bytes(int nx, int nu) { return (pnqp_tiled_lds_floats(nu) + (size_t)(nx + nu)) * sizeof(float); }
+static int launch_sweep_tiled(const MpcSweepJob &j, hipStream_t stream) {
+  return launch_kernel(mpc_tiled_backward_kernel, dim3(j.a.B), dim3(kTiledThreads), sweep_tiled_lds_bytes(j.nx, j.nu), stream, j.a,
+                       j.nx, j.nu, j.a.tiled_scratch);
+}
+
+// Both generated streams in one launch (mpc_step_fused_kernel.hpp)
+template <int NX, int NU>
+static int launch_step_fused(const MpcBackArgs &ba, const MpcFwdArgs &fa, hipStream_t stream) {
+  return with_sweep_form(ba, [&](auto has_f, auto recentre) {
+    return launch_kernel(mpc_step_fused_asm_kernel<NX, NU, decltype(has_f)::value, decltype(recentre)::value>, dim3((ba.B + 15) / 16),
+                         dim3(256), mpc_step_fused_lds_bytes<NX, NU>(), stream, ba, fa);
+  });
+}
 
 // rollout + linearisation of the built-in pendulum: four lanes per trajectory when the 16-byte row accesses are aligned
 static void launch_pendulum_rollout(const PendulumArgs &pa, hipStream_t stream) {
@@ -377,157 +402,273 @@ static void launch_pendulum_rollout(const PendulumArgs &pa, hipStream_t stream) 
     DMPC_LAUNCH_GGL(pendulum_rollout_linearize_kernel, dim3((pa.B + 63) / 64), dim3(64), 0, stream, pa);
 }
 
-static int launch_mpc_fwd(int nx, int nu, const MpcFwdArgs &a_in, hipStream_t stream) {
-  MpcFwdArgs a = a_in;
-  if (a.dyn_kind == 1 && nx == 3 && nu == 1 && !knob_on<Knob::DMPC_NO_SPEC_LS>()) {
-    // the pendulum's line search usually walks ten or more step sizes: 16 candidates per trajectory at once; every
-    // candidate keeps its trajectory in LDS (T * 4 KB per workgroup) when that fits
-    if (a.T <= kSpec4MaxT && !knob_on<Knob::DMPC_NO_SPEC4>()) {   // a wavefront per trajectory, all inputs and candidates in LDS
-      DMPC_LAUNCH_GGL(mpc_forward_rec_pendulum_spec4_kernel, dim3((a.B + 3) / 4), dim3(256),
-                         Spec4Layout::lds_bytes(a.T), stream, a);
-      return (int)hipGetLastError();
-    }
-    const size_t lds = (size_t)a.T * 4 * 256 * sizeof(float);
-    a.traj_in_lds = lds <= 96 * 1024 ? 1 : 0;
-    const bool dma = a.B >= 4 && a.B % 4 == 0 && !knob_on<Knob::DMPC_NO_MPC_DMA>() &&
-                     aligned16(a.C, a.c, a.Ks, a.ks, a.controls, a.lower, a.upper, a.states);
-    if (dma)
-      DMPC_LAUNCH_GGL(mpc_forward_rec_pendulum_spec_kernel<true>, dim3((a.B + 15) / 16), dim3(256),
-                         (a.traj_in_lds ? lds : 0) + SpecDmaLayout::lds_bytes(), stream, a);
-    else
-      DMPC_LAUNCH_GGL(mpc_forward_rec_pendulum_spec_kernel<false>, dim3((a.B + 15) / 16), dim3(256),
-                         a.traj_in_lds ? lds : 0, stream, a);
-    return (int)hipGetLastError();
+// The pendulum's line search usually walks ten or more step sizes.  A wavefront per trajectory, all inputs and candidates in LDS ...
+static int launch_search_spec4(const MpcSearchJob &j, hipStream_t stream) {
+  return launch_kernel(mpc_forward_rec_pendulum_spec4_kernel, dim3((j.a.B + 3) / 4), dim3(256), Spec4Layout::lds_bytes(j.a.T), stream, j.a);
+}
+// ... or 16 candidates per trajectory at once; every candidate keeps its trajectory in LDS (T * 4 KB per workgroup) when that fits
+template <bool DMA>
+static int launch_search_spec(const MpcSearchJob &j, hipStream_t stream) {
+  MpcFwdArgs a = j.a;
+  const size_t lds = (size_t)a.T * 4 * 256 * sizeof(float);
+  a.traj_in_lds = lds <= 96 * 1024 ? 1 : 0;
+  return launch_kernel(mpc_forward_rec_pendulum_spec_kernel<DMA>, dim3((a.B + 15) / 16), dim3(256),
+                       (a.traj_in_lds ? lds : 0) + (DMA ? SpecDmaLayout::lds_bytes() : 0), stream, a);
+}
+
+// the line search as one generated instruction stream (mpc_fwd_asm_kernel.hpp)
+template <int NX, int NU>
+static int launch_search_stream(const MpcSearchJob &j, hipStream_t stream) {
+  return launch_kernel(mpc_forward_asm_kernel<NX, NU>, dim3((j.a.B + 15) / 16), dim3(256), mpc_fwd_asm_lds_bytes<NX, NU>(), stream, j.a);
+}
+
+// mpc_forward_rec_kernel: a lane group per trajectory.  DMA: inputs through the LDS-DMA ring; PAD: a container
+template <int NX, int NU, int L, bool DMA, bool PAD>
+static int launch_search_rows(const MpcSearchJob &j, hipStream_t stream) {
+  constexpr int GPB = 256 / L;
+  size_t lds = 0;
+  if constexpr (DMA) lds = MpcFwdDmaLayout<NX, NU>::lds_bytes();
+  const MpcFwdArgs a = told_dims(j.a, PAD, j.nx, j.nu);
+  return launch_kernel(mpc_forward_rec_kernel<NX, NU, L, DMA, PAD>, dim3((a.B + GPB - 1) / GPB), dim3(256), lds, stream, a);
+}
+
+// 17 to 31 elements of tau, at most 16 states: the line search of the wide row layout (mpc_wide_forward_kernel.hpp: four
+// trajectories per wavefront; before, the runtime-dimension kernel - 0.68 ms at (12,4)), padded shapes as the sweep's
+template <int NX, int NU>
+static int launch_search_wide(const MpcSearchJob &j, hipStream_t stream) {
+  using Lay = MpcWideFwdLayout<NX, NU, 2>;
+  static_assert(Lay::lds_bytes() <= 160 * 1024, "ring beyond a CU's LDS");
+  const bool pad = j.nx != NX || j.nu != NU;
+  const MpcFwdArgs a = told_dims(j.a, pad, j.nx, j.nu);
+  return with_bools([&](auto PAD) {
+    return launch_kernel_big_lds(mpc_wide_forward_kernel<NX, NU, 2, decltype(PAD)::value>, dim3((a.B + 15) / 16), dim3(256),
+                                 Lay::lds_bytes(), stream, a);
+  }, pad);
+}
+
+// the runtime-dimension kernels (mpc_generic.hpp): the inputs of a step through an LDS ring, or fetched row by row
+static int launch_search_staged(const MpcSearchJob &j, hipStream_t stream) {
+  return launch_kernel_big_lds(mpc_staged_forward_kernel, dim3(j.a.B), dim3(64), mpc_staged_fwd_lds_bytes(j.nx, j.nu), stream, j.a, j.nx, j.nu);
+}
+static int launch_search_generic(const MpcSearchJob &j, hipStream_t stream) {
+  return launch_kernel(mpc_generic_forward_kernel, dim3(j.a.B), dim3(64), mpc_generic_fwd_lds_bytes(j.nx, j.nu), stream, j.a, j.nx, j.nu);
+}
+static size_t search_tiled_lds_bytes(int nx, int nu) { return (size_t)(2 * nx + 2 * (nx + nu) + 4) * sizeof(float); }
+static int launch_search_tiled(const MpcSearchJob &j, hipStream_t stream) {
+  return launch_kernel(mpc_tiled_forward_kernel, dim3(j.a.B), dim3(kTiledThreads), search_tiled_lds_bytes(j.nx, j.nu), stream, j.a, j.nx, j.nu);
+}
+
+// ---- The routes: which kernel takes the sweep (MPCstep.backward_rec) and which the line search (forward_rec) of a call.
+// They take values only, launch nothing and dereference nothing, and every entry point asks them for all it will launch
+// before its first launch: a refused call has launched nothing.  (The form of a sweep - with f_hat, re-centring - picks no
+// kernel family: every stream has all three, so its launcher reads it from the arguments.)
+struct MpcSweepCall {
+  int T, B, nx, nu;
+  bool coupled;        // batch-coupled termination of the box QPs (a.sync)
+  bool in_ddp_loop;    // a step of the device-driven BoxDDP loop: a `done` flag, or flags stored instead of or-ed
+  bool select;         // ... with the bookkeeping of the iteration before riding along (MpcSweepJob::sel)
+  bool ring_aligned;   // what the LDS-DMA ring fetches is 16-byte aligned: C, c, F, f, controls, lower, upper, states
+  bool wide_aligned;   // what the wide row kernel fetches by 16 bytes is: C, c, F, f
+  bool scratch;        // the caller has a tiled scratch to give
+};
+struct MpcSearchCall {
+  int T, B, nx, nu;
+  int dyn_kind;        // 0: LinDx (F, f); 1: the built-in pendulum
+  bool ls_cap;         // a cap on the step sizes tried (the streams and the wide kernel need one)
+  bool info_in;        // the sweep's flags arrive through a staging word (BoxDDP's fused chain)
+  bool ring_aligned;   // C, c, F, f, Ks, ks, controls, lower, upper, states (the pendulum has no F, f: absent counts as aligned)
+};
+enum class MpcKernel { kOther, kStream, kRing, kSpec4 };
+struct MpcSweepRoute {
+  int code;                            // 0, or the DMPC_E_* of a refusal
+  MpcSweepLauncher launch = nullptr;
+  MpcKernel kind = MpcKernel::kOther;
+  bool needs_scratch = false;          // a.tiled_scratch is read: the tiled kernel, and every batch-coupled call (the fixed grid)
+  MpcStepLauncher fused = nullptr;     // kStream: the launch that also holds the search's stream
+};
+struct MpcSearchRoute {
+  int code;
+  MpcSearchLauncher launch = nullptr;
+  MpcKernel kind = MpcKernel::kOther;
+};
+
+// four trajectories per wavefront: at least one whole wavefront and a horizon with an F ...
+static bool fills_a_wave(int T, int B) { return B >= 4 && T >= 2; }
+// ... and, for what goes through an LDS-DMA ring or runs padded, no ragged last wavefront
+static bool whole_waves(int B) { return B >= 4 && B % 4 == 0; }
+// the wide row kernels index a time step by 32 bits
+static bool wide_strides_fit(int B, int nx, int nu) { return (size_t)B * (nx + nu) * (nx + nu) * 4 < ((size_t)1 << 31); }
+// the runtime-dimension kernels: a wavefront's lanes hold the columns, the QP up to eight controls; beyond: mpc_tiled.hpp
+static bool runtime_dims_fit(int nx, int nu) { return nx + nu + 1 <= 64 && nu <= kMpcGenericMaxNu; }
+
+// the wide instance (index into DMPC_MPC_WIDE_SHAPES) that takes the shape - its own, or the smallest that holds a shape of
+// mpc_wide_padded, whole wavefronts only - or -1
+static int wide_instance(int B, int nx, int nu) {
+  constexpr int dims[][2] = {
+#define X(NX_, NU_) {NX_, NU_},
+      DMPC_MPC_WIDE_SHAPES(X)
+#undef X
+  };
+  for (int i = 0; i < 4; ++i)
+    if (nx == dims[i][0] && nu == dims[i][1]) return i;
+  if (!(nx >= 1 && nu >= 1 && mpc_wide_padded(nx, nu) && B % 4 == 0 && !knob_on<Knob::DMPC_NO_CONTAINER>())) return -1;
+  for (int i = 0; i < 4; ++i)
+    if (nx <= dims[i][0] && nu <= dims[i][1]) return i;
+  return -1;
+}
+#define X(NX_, NU_) launch_sweep_wide<NX_, NU_>,
+static constexpr MpcSweepLauncher kSweepWide[] = {DMPC_MPC_WIDE_SHAPES(X)};
+#undef X
+#define X(NX_, NU_) launch_search_wide<NX_, NU_>,
+static constexpr MpcSearchLauncher kSearchWide[] = {DMPC_MPC_WIDE_SHAPES(X)};
+#undef X
+
+// a shape with a 16-lane specialisation of its own: through the ring, else (and batch-coupled) on the register banks
+template <int NX, int NU, int L>
+static MpcSweepRoute sweep_route_exact(const MpcSweepCall &q, bool ring) {
+  if constexpr (L == 16 && SweepRing<NX, NU>::kFits) {
+    if (ring) return {0, launch_sweep_ring<NX, NU>, MpcKernel::kRing};
   }
-  // LinDx, whole wavefronts of four trajectories, 16-byte aligned runs: inputs through the LDS-DMA ring
-  const bool fwd_dma = a.dyn_kind == 0 && a.B >= 4 && a.B % 4 == 0 && !knob_on<Knob::DMPC_NO_MPC_DMA>() &&
-                       aligned16(a.C, a.c, a.F, a.f, a.Ks, a.ks, a.controls, a.lower, a.upper, a.states);
-  // the line search as one generated instruction stream (mpc_fwd_asm_kernel.hpp); DMPC_NO_MPC_ASM=1: the HIP kernels
-  if (fwd_dma && a.ls_cap > 0 && !knob_on<Knob::DMPC_NO_MPC_ASM>()) {
-    const dim3 grid((a.B + 15) / 16), block(256);
-#define A(NX_, NU_)                                                                                          \
-  if (nx == NX_ && nu == NU_) {                                                                              \
-    DMPC_LAUNCH_GGL((mpc_forward_asm_kernel<NX_, NU_>), grid, block, (mpc_fwd_asm_lds_bytes<NX_, NU_>()), stream, a); \
-    return (int)hipGetLastError();                                                                           \
-  }
-    A(8, 2) A(3, 1) A(4, 2) A(6, 2) A(2, 2) A(1, 1) A(2, 1) A(3, 2)
+  if (q.select) return {DMPC_E_BADARG};
+  return {0, launch_sweep_rows<NX, NU, L, false>, MpcKernel::kOther, q.coupled};
+}
+
+static MpcSweepRoute mpc_sweep_route(const MpcSweepCall &q) {
+  const int nx = q.nx, nu = q.nu;
+  // per-trajectory termination, whole wavefronts of four trajectories, 16-byte aligned runs: inputs through the LDS-DMA
+  // ring of mpc_dma_kernels.hpp (DMPC_NO_MPC_DMA=1: the register-bank kernel, for A/B timing)
+  const bool ring = !q.coupled && whole_waves(q.B) && !knob_on<Knob::DMPC_NO_MPC_DMA>() && q.ring_aligned;
+  if (q.select && !ring) return {DMPC_E_BADARG};   // (BoxDDP asks with `select` only after a route that took the ring)
+  // The sweep as one generated instruction stream: shapes the generator covers.  DMPC_NO_MPC_ASM=1: the HIP kernels (A/B timing).
+  if (ring && q.T >= 2 && !knob_on<Knob::DMPC_NO_MPC_ASM>()) {
+#define A(NX_, NU_) \
+  if (nx == NX_ && nu == NU_) return {0, launch_sweep_stream<NX_, NU_>, MpcKernel::kStream, false, launch_step_fused<NX_, NU_>};
+    DMPC_MPC_STREAM_SHAPES(A, DMPC_NO_SHAPE)
 #undef A
   }
-#define X(NX_, NU_, L_)                                                                                      \
-  if (nx == NX_ && nu == NU_) {                                                                              \
-    constexpr int GPB = 256 / L_;                                                                            \
-    if constexpr (L_ == 16 && MpcFwdDmaLayout<NX_, NU_>::lds_bytes() <= 96 * 1024) {                          \
-      if (fwd_dma) {                                                                                         \
-        DMPC_LAUNCH_GGL((mpc_forward_rec_kernel<NX_, NU_, L_, true>), dim3((a.B + GPB - 1) / GPB), dim3(256), \
-                           (MpcFwdDmaLayout<NX_, NU_>::lds_bytes()), stream, a);                             \
-        return (int)hipGetLastError();                                                                       \
-      }                                                                                                      \
-    }                                                                                                        \
-    DMPC_LAUNCH_GGL((mpc_forward_rec_kernel<NX_, NU_, L_>), dim3((a.B + GPB - 1) / GPB), dim3(256), 0, stream, \
-                       a);                                                                                   \
-    return (int)hipGetLastError();                                                                           \
-  }
+#define X(NX_, NU_, L_) \
+  if (nx == NX_ && nu == NU_) return sweep_route_exact<NX_, NU_, L_>(q, ring);
   DMPC_MPC_SHAPES(X)
 #undef X
-  // 17 to 31 elements of tau, at most 16 states: the line search of the wide row layout (mpc_wide_forward_kernel.hpp: four
-  // trajectories per wavefront; before, the runtime-dimension kernel - 0.68 ms at (12,4)).  DMPC_NO_WIDE=1: that one.
-  {
-    if (!knob_on<Knob::DMPC_NO_WIDE>() && a.dyn_kind == 0 && a.ls_cap > 0 && a.B >= 4 && a.T >= 2 && a.info_in == nullptr &&
-        aligned16(a.C, a.c, a.F, a.f, a.Ks, a.ks, a.controls, a.lower, a.upper, a.states) &&
-        (size_t)a.B * (nx + nu) * (nx + nu) * 4 < ((size_t)1 << 31)) {
-#define X(NX_, NU_)                                                                                            \
-  if (nx == NX_ && nu == NU_) {                                                                                \
-    using Lay = MpcWideFwdLayout<NX_, NU_, 2>;                                                                 \
-    static_assert(Lay::lds_bytes() <= 160 * 1024, "ring beyond a CU's LDS");                                   \
-    if (Lay::lds_bytes() > 64 * 1024)                                                                          \
-      set_max_lds(reinterpret_cast<const void *>(&mpc_wide_forward_kernel<NX_, NU_, 2>), \
-                                (int)Lay::lds_bytes());           \
-    DMPC_LAUNCH_GGL((mpc_wide_forward_kernel<NX_, NU_, 2>), dim3((a.B + 15) / 16), dim3(256), Lay::lds_bytes(), stream, a); \
-    return (int)hipGetLastError();                                                                             \
+  if (q.select) return {DMPC_E_BADARG};   // (bookkeeping rides in the stream and ring kernels alone)
+  // DMPC_NO_WIDE=1: the kernels below
+  if (!knob_on<Knob::DMPC_NO_WIDE>() && !q.coupled && fills_a_wave(q.T, q.B) && q.wide_aligned && wide_strides_fit(q.B, nx, nu)) {
+    if (const int i = wide_instance(q.B, nx, nu); i >= 0) return {0, kSweepWide[i]};
   }
-      X(12, 4) X(16, 4) X(12, 8) X(16, 8)
+  // the matrix-core sweep: per-trajectory termination, not inside the device-driven BoxDDP loop (no `done` flag there)
+  const bool wave = !q.coupled && !q.in_ddp_loop && !knob_on<Knob::DMPC_NO_MPC_WAVE>();
+  if (wave && ((nx == 16 && nu == 8) || (nx == 32 && nu == 8)) && q.T >= 1) return {0, launch_sweep_wave};
+  if (!knob_on<Knob::DMPC_NO_CONTAINER>()) {   // a smaller problem inside the first container that holds it
+#define X(NX_, NU_) \
+  if (nx <= NX_ && nu <= NU_) return {0, launch_sweep_rows<NX_, NU_, 16, true>, MpcKernel::kOther, q.coupled};
+    DMPC_MPC_CONTAINERS(X)
 #undef X
-      if (nx >= 1 && nu >= 1 && nx <= 16 && nu <= 8 && mpc_wide_padded(nx, nu) && a.B % 4 == 0 &&
-          !knob_on<Knob::DMPC_NO_CONTAINER>()) {
-        MpcFwdArgs p = a;     // ... and padded inside the smallest of those instances (as the sweep)
-        p.nx_log = nx;
-        p.nu_log = nu;
-#define X(NX_, NU_)                                                                                            \
-  if (nx <= NX_ && nu <= NU_) {                                                                                \
-    using Lay = MpcWideFwdLayout<NX_, NU_, 2>;                                                                 \
-    if (Lay::lds_bytes() > 64 * 1024)                                                                          \
-      set_max_lds(reinterpret_cast<const void *>(&mpc_wide_forward_kernel<NX_, NU_, 2, true>), \
-                                (int)Lay::lds_bytes());           \
-    DMPC_LAUNCH_GGL((mpc_wide_forward_kernel<NX_, NU_, 2, true>), dim3((p.B + 15) / 16), dim3(256), Lay::lds_bytes(), stream, p); \
-    return (int)hipGetLastError();                                                                             \
-  }
-        X(12, 4) X(16, 4) X(12, 8) X(16, 8)
-#undef X
-      }
+    // A padded wave instance costs what ITS shape costs (and fetches element by element, one wavefront per SIMD): measured at
+    // B = 4096, T = 50 it beats the runtime-dimension kernel where the latter's QP in lane 0 is widest - (24,8) 9.2 against
+    // 12.5 ms - and lost below - (20,6) 7.8 against 5.4 ms, (10,5) 5.4 against 2.9 ms.
+    // (Round 4, the padded instance fetching through its LDS-DMA slot: (20,6) 3.4 against 3.8 ms - six controls and more.)
+    // (Round 5, from 21 states on with three to five controls, from 24 with one or two: the runtime-dimension kernel's cost grows with nx^2 in one lane group -
+    // (32,4) 7.7 ms, (32,2) 6.4, (23,4) 4.2, (24,4) 3.9 - where the padded (32,8) instance stays at ~3 ms: (32,4) 3.1, (32,2) 2.8, (24,4) 3.0.)
+    const bool small = nu <= 4 && nx + nu <= 15;     // (the 16-lane containers above take these)
+    if (wave && !small && nx <= 32 && nu <= 8) {
+      if (nu >= 6 && nx <= 16) return {0, launch_sweep_wave_container<16, 8>};
+      if (nu >= 6 || nx >= (nu >= 3 ? 21 : 24)) return {0, launch_sweep_wave_container<32, 8>};
     }
   }
-  if (a.dyn_kind == 0 && !knob_on<Knob::DMPC_NO_CONTAINER>()) {
-    a.nx_log = nx;
-    a.nu_log = nu;
-#define X(NX_, NU_)                                                                                              \
-  if (nx <= NX_ && nu <= NU_) {                                                                                  \
-    DMPC_LAUNCH_GGL((mpc_forward_rec_kernel<NX_, NU_, 16, false, true>), dim3((a.B + 15) / 16), dim3(256), 0, stream, a); \
-    return (int)hipGetLastError();                                                                               \
+  if (runtime_dims_fit(nx, nu)) {
+#define X(NU_) \
+  if (nu == NU_) return {0, launch_sweep_generic<NU_>, MpcKernel::kOther, q.coupled};
+    DMPC_ONE_TO_EIGHT(X)
+#undef X
   }
+  // any other size (more than 8 controls, more than 64 columns): a workgroup per trajectory, matrices in the caller's
+  // workspace (mpc_tiled.hpp; batch-coupled: mpc_coupled.hpp)
+  if (!q.scratch) return {DMPC_E_WORKSPACE, nullptr, MpcKernel::kOther, true};
+  if (q.coupled) return {0, launch_sweep_fixed_grid, MpcKernel::kOther, true};
+  if (sweep_tiled_lds_bytes(nx, nu) > 60 * 1024) return {DMPC_E_UNSUPPORTED, nullptr, MpcKernel::kOther, true};
+  return {0, launch_sweep_tiled, MpcKernel::kOther, true};
+}
+
+template <int NX, int NU, int L>
+static MpcSearchRoute search_route_exact(bool ring) {
+  if constexpr (L == 16 && search_ring_fits<NX, NU>()) {
+    if (ring) return {0, launch_search_rows<NX, NU, L, true, false>, MpcKernel::kRing};
+  }
+  return {0, launch_search_rows<NX, NU, L, false, false>};
+}
+
+static MpcSearchRoute mpc_search_route(const MpcSearchCall &q) {
+  const int nx = q.nx, nu = q.nu;
+  const bool lin = q.dyn_kind == 0;
+  // whole wavefronts of four trajectories, 16-byte aligned runs: inputs through an LDS-DMA ring
+  const bool ring = whole_waves(q.B) && !knob_on<Knob::DMPC_NO_MPC_DMA>() && q.ring_aligned;
+  if (q.dyn_kind == 1 && nx == 3 && nu == 1 && !knob_on<Knob::DMPC_NO_SPEC_LS>()) {
+    if (q.T <= kSpec4MaxT && !knob_on<Knob::DMPC_NO_SPEC4>()) return {0, launch_search_spec4, MpcKernel::kSpec4};
+    return {0, ring ? launch_search_spec<true> : launch_search_spec<false>};
+  }
+  // DMPC_NO_MPC_ASM=1: the HIP kernels
+  if (lin && ring && q.ls_cap && !knob_on<Knob::DMPC_NO_MPC_ASM>()) {
+#define A(NX_, NU_) \
+  if (nx == NX_ && nu == NU_) return {0, launch_search_stream<NX_, NU_>, MpcKernel::kStream};
+    DMPC_MPC_STREAM_SHAPES(A, A)
+#undef A
+  }
+#define X(NX_, NU_, L_) \
+  if (nx == NX_ && nu == NU_) return search_route_exact<NX_, NU_, L_>(lin && ring);
+  DMPC_MPC_SHAPES(X)
+#undef X
+  if (!lin) return {DMPC_E_UNSUPPORTED};   // (a built-in dynamics has the kernels of its own shape alone)
+  // DMPC_NO_WIDE=1: the kernels below
+  if (!knob_on<Knob::DMPC_NO_WIDE>() && q.ls_cap && fills_a_wave(q.T, q.B) && !q.info_in && q.ring_aligned &&
+      wide_strides_fit(q.B, nx, nu)) {
+    if (const int i = wide_instance(q.B, nx, nu); i >= 0) return {0, kSearchWide[i]};
+  }
+  if (!knob_on<Knob::DMPC_NO_CONTAINER>()) {
+#define X(NX_, NU_) \
+  if (nx <= NX_ && nu <= NU_) return {0, launch_search_rows<NX_, NU_, 16, false, true>};
     DMPC_MPC_CONTAINERS(X)
 #undef X
   }
-  if (a.dyn_kind == 0 && nx + nu + 1 <= 64 && nu <= kMpcGenericMaxNu && !knob_on<Knob::DMPC_NO_MPC_STAGED_FWD>()) {
-    // the inputs of a step through an LDS ring (mpc_staged_forward_kernel); DMPC_NO_MPC_STAGED_FWD=1: the kernel below
-    const size_t shmem = mpc_staged_fwd_lds_bytes(nx, nu);
-    if (shmem <= 150 * 1024) {
-      if (shmem > 64 * 1024)
-        set_max_lds(reinterpret_cast<const void *>(&mpc_staged_forward_kernel), (int)shmem);
-      DMPC_LAUNCH_GGL(mpc_staged_forward_kernel, dim3(a.B), dim3(64), shmem, stream, a, nx, nu);
-      return (int)hipGetLastError();
-    }
+  if (runtime_dims_fit(nx, nu)) {
+    // the inputs of a step through an LDS ring (mpc_staged_forward_kernel); DMPC_NO_MPC_STAGED_FWD=1: fetched row by row
+    if (!knob_on<Knob::DMPC_NO_MPC_STAGED_FWD>() && mpc_staged_fwd_lds_bytes(nx, nu) <= 150 * 1024) return {0, launch_search_staged};
+    return {0, launch_search_generic};
   }
-  if (a.dyn_kind == 0 && nx + nu + 1 <= 64 && nu <= kMpcGenericMaxNu) {
-    DMPC_LAUNCH_GGL(mpc_generic_forward_kernel, dim3(a.B), dim3(64), mpc_generic_fwd_lds_bytes(nx, nu), stream, a,
-                       nx, nu);
-    return (int)hipGetLastError();
+  if (search_tiled_lds_bytes(nx, nu) > 60 * 1024) return {DMPC_E_UNSUPPORTED};   // any other size: mpc_tiled.hpp
+  return {0, launch_search_tiled};
+}
+
+// the values of a call, read off its arguments once
+static MpcSweepCall sweep_call(int nx, int nu, const MpcBackArgs &a, bool select, bool scratch) {
+  return {a.T, a.B, nx, nu, a.sync != nullptr, a.done != nullptr || a.info_store != 0, select,
+          aligned16(a.C, a.c, a.F, a.f, a.controls, a.lower, a.upper, a.states), aligned16(a.C, a.c, a.F, a.f), scratch};
+}
+static MpcSearchCall search_call(int nx, int nu, const MpcFwdArgs &a) {
+  return {a.T, a.B, nx, nu, a.dyn_kind, a.ls_cap > 0, a.info_in != nullptr,
+          aligned16(a.C, a.c, a.F, a.f, a.Ks, a.ks, a.controls, a.lower, a.upper, a.states)};
+}
+// does a sweep of this size read a tiled scratch?  (No switch and no alignment moves a shape on or off the tiled kernel.)
+static bool sweep_needs_scratch(int T, int B, int nx, int nu) {
+  return mpc_sweep_route({T, B, nx, nu, false, false, false, false, false, true}).needs_scratch;
+}
+// Both generated streams in one launch when each route answered with its stream.  DMPC_NO_MPC_FUSED=1: two launches (A/B).
+static MpcStepLauncher fused_step(const MpcSweepRoute &sweep, const MpcSearchRoute &search) {
+  return search.kind == MpcKernel::kStream && !knob_on<Knob::DMPC_NO_MPC_FUSED>() ? sweep.fused : nullptr;
+}
+
+static int run_sweep(const MpcSweepRoute &r, int nx, int nu, const MpcBackArgs &a, hipStream_t stream, const DdpSelectArgs *sel = nullptr,
+                     unsigned *sel_sync = nullptr) {
+  if (a.sync != nullptr) {   // fresh decision slots for this launch
+    const hipError_t e = hipMemsetAsync(a.sync, 0, coupled_bytes(a.T, a.n_qp_iter), stream);
+    if (e != hipSuccess) return (int)e;
   }
-  if (a.dyn_kind == 0) {   // any other size: mpc_tiled.hpp
-    const size_t shmem = (size_t)(2 * nx + 2 * (nx + nu) + 4) * sizeof(float);
-    if (shmem > 60 * 1024) return DMPC_E_UNSUPPORTED;
-    DMPC_LAUNCH_GGL(mpc_tiled_forward_kernel, dim3(a.B), dim3(kTiledThreads), shmem, stream, a, nx, nu);
-    return (int)hipGetLastError();
-  }
-  return DMPC_E_UNSUPPORTED;
+  return r.launch({a, nx, nu, sel, sel_sync}, stream);
 }
 
 struct MpcWs {
   size_t c_back, neg, x0, dx, du, mask, sync, tiled, lqr, total;
 };
 constexpr int kSyncQpIterMax = 64;   // the workspace queries do not know n_qp_iter_max: sized for up to this many
-// Both generated streams in one launch (mpc_step_fused_kernel.hpp) when each of them would have been chosen on its own:
-// the conditions of launch_mpc_back's and launch_mpc_fwd's stream branches.  DMPC_NO_MPC_FUSED=1: two launches (A/B).
-static int launch_mpc_step_fused(int nx, int nu, const MpcBackArgs &ba, const MpcFwdArgs &fa, hipStream_t stream) {
-  if (knob_on<Knob::DMPC_NO_MPC_FUSED>() || knob_on<Knob::DMPC_NO_MPC_ASM>() || !mpc_back_dma_ok(ba) || ba.T < 2 ||
-      !(ba.states == nullptr || ba.f == nullptr))
-    return DMPC_E_UNSUPPORTED;
-  if (!(fa.dyn_kind == 0 && fa.ls_cap > 0 &&
-        aligned16(fa.C, fa.c, fa.F, fa.f, fa.Ks, fa.ks, fa.controls, fa.lower, fa.upper, fa.states)))
-    return DMPC_E_UNSUPPORTED;
-  const dim3 grid((ba.B + 15) / 16), block(256);
-  const int variant = ba.states != nullptr ? 2 : (ba.f != nullptr ? 1 : 0);   // re-centring / with f_hat / plain
-#define A(NX_, NU_)                                                                                              \
-  if (nx == NX_ && nu == NU_) {                                                                                  \
-    constexpr size_t lds = mpc_step_fused_lds_bytes<NX_, NU_>();                                                 \
-    if (variant == 2) DMPC_LAUNCH_GGL((mpc_step_fused_asm_kernel<NX_, NU_, false, true>), grid, block, lds, stream, ba, fa); \
-    else if (variant == 1) DMPC_LAUNCH_GGL((mpc_step_fused_asm_kernel<NX_, NU_, true, false>), grid, block, lds, stream, ba, fa); \
-    else DMPC_LAUNCH_GGL((mpc_step_fused_asm_kernel<NX_, NU_, false, false>), grid, block, lds, stream, ba, fa); \
-    return (int)hipGetLastError();                                                                               \
-  }
-  A(8, 2) A(3, 1) A(4, 2) A(2, 2) A(1, 1) A(2, 1) A(3, 2)
-#undef A
-  return DMPC_E_UNSUPPORTED;
-}
 
 static MpcWs mpc_layout(int T, int B, int nx, int nu) {
   const size_t ns = nx + nu;
@@ -683,34 +824,27 @@ int dmpc_pnqp(int B, int n, const float *H, const float *q, const float *lower, 
     void *targs[] = {&ta, &vecs, &sync};
     return launch_fixed_grid(reinterpret_cast<const void *>(&pnqp_coupled_kernel), B, targs, stream);
   };
-  switch (n) {
-#define CASE(N)                                                                                                  \
-  case N:                                                                                                        \
-    if (sync != nullptr) {                                                                                       \
-      const int rc = knob_on_now<Knob::DMPC_NO_COOP_REGISTER>()                                                  \
-                         ? DMPC_E_UNSUPPORTED                                                                    \
-                         : launch_cooperative(reinterpret_cast<const void *>(&pnqp_kernel<N>), grid, block, args, 0, stream); \
-      return rc == DMPC_E_UNSUPPORTED ? fixed_grid() : rc;                                                       \
-    }                                                                                                            \
-    DMPC_LAUNCH_GGL((pnqp_kernel<N>), grid, block, 0, stream, a);                                             \
-    break;
-    CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-#undef CASE
-    default: {   // any n: a workgroup per QP (mpc_tiled.hpp; batch-coupled: mpc_coupled.hpp)
-      if (sync != nullptr) return fixed_grid();
-      const size_t shmem = pnqp_tiled_lds_floats(n) * sizeof(float);
-      if (shmem > 60 * 1024) return DMPC_E_UNSUPPORTED;
-      PnqpTiledArgs ta{B, n, H, q, lower, upper, x_init, n_iter, x, fac, piv, index_f, n_iter_out, info};
-      DMPC_LAUNCH_GGL(pnqp_tiled_kernel, dim3(B), dim3(kTiledThreads), shmem, stream, ta);
-    }
+  void (*kernel)(const PnqpArgs) = nullptr;   // up to eight unknowns: a lane per QP
+#define X(N_) \
+  if (n == N_) kernel = pnqp_kernel<N_>;
+  DMPC_ONE_TO_EIGHT(X)
+#undef X
+  if (kernel != nullptr) {
+    if (sync == nullptr) return launch_kernel(kernel, grid, block, 0, stream, a);
+    return launch_coupled(reinterpret_cast<const void *>(kernel), grid, block, args, 0, stream, fixed_grid);
   }
-  return (int)hipGetLastError();
+  // any n: a workgroup per QP (mpc_tiled.hpp; batch-coupled: mpc_coupled.hpp)
+  if (sync != nullptr) return fixed_grid();
+  const size_t shmem = pnqp_tiled_lds_floats(n) * sizeof(float);
+  if (shmem > 60 * 1024) return DMPC_E_UNSUPPORTED;
+  PnqpTiledArgs ta{B, n, H, q, lower, upper, x_init, n_iter, x, fac, piv, index_f, n_iter_out, info};
+  return launch_kernel(pnqp_tiled_kernel, dim3(B), dim3(kTiledThreads), shmem, stream, ta);
 }
 
 size_t dmpc_mpc_backward_rec_workspace_bytes(int T, int B, int nx, int nu, int n_qp_iter_max, int batch_coupled) {
   if (T <= 0 || B <= 0 || nx <= 0 || nu <= 0) return 0;
   if (batch_coupled) return coupled_bytes(T, n_qp_iter_max) + coupled_traj_bytes(B, nx, nu);
-  return mpc_needs_tiles(nx, nu) ? (size_t)B * mpc_tiled_scratch_floats(nx, nu) * sizeof(float) : 0;
+  return sweep_needs_scratch(T, B, nx, nu) ? (size_t)B * mpc_tiled_scratch_floats(nx, nu) * sizeof(float) : 0;
 }
 
 int dmpc_mpc_backward_rec(int T, int B, int nx, int nu, const float *C_hat, const float *c_hat,
@@ -724,12 +858,12 @@ int dmpc_mpc_backward_rec(int T, int B, int nx, int nu, const float *C_hat, cons
   if (batch_coupled && (!ws || ws_bytes < dmpc_mpc_backward_rec_workspace_bytes(T, B, nx, nu, n_qp_iter_max, 1))) return DMPC_E_WORKSPACE;
   MpcBackArgs ba{T, B, C_hat, c_hat, F_hat, f_hat, controls, u_lower, u_upper, n_qp_iter_max, Ks_out, ks_out,
                  n_qp_iter, info, nullptr, batch_coupled ? static_cast<unsigned *>(ws) : nullptr, nullptr};
-  if (batch_coupled) ba.tiled_scratch = reinterpret_cast<float *>(static_cast<char *>(ws) + coupled_bytes(T, n_qp_iter_max));
-  if (!batch_coupled && mpc_needs_tiles(nx, nu)) {
-    if (!ws || ws_bytes < dmpc_mpc_backward_rec_workspace_bytes(T, B, nx, nu, n_qp_iter_max, 0)) return DMPC_E_WORKSPACE;
-    ba.tiled_scratch = static_cast<float *>(ws);
-  }
-  return launch_mpc_back(nx, nu, ba, static_cast<hipStream_t>(stream_));
+  const bool scratch = batch_coupled || (ws && ws_bytes >= (size_t)B * mpc_tiled_scratch_floats(nx, nu) * sizeof(float));
+  const MpcSweepRoute r = mpc_sweep_route(sweep_call(nx, nu, ba, false, scratch));
+  if (r.code != 0) return r.code;
+  if (r.needs_scratch)   // (batch-coupled: behind the decision slots)
+    ba.tiled_scratch = reinterpret_cast<float *>(static_cast<char *>(ws) + (batch_coupled ? coupled_bytes(T, n_qp_iter_max) : 0));
+  return run_sweep(r, nx, nu, ba, static_cast<hipStream_t>(stream_));
 }
 
 int dmpc_mpc_forward_rec(int T, int B, int nx, int nu, const float *Ks, const float *ks, const float *controls,
@@ -745,7 +879,8 @@ int dmpc_mpc_forward_rec(int T, int B, int nx, int nu, const float *Ks, const fl
   if (!aligned16(C_true) || !aligned16(F_true)) return DMPC_E_BADARG;
   MpcFwdArgs fa{T, B, Ks, ks, controls, states, u_lower, u_upper, C_true, c_true, F_true, f_true, ls_decay,
                 max_ls_iter, /*ls_cap=*/64, x_out, u_out, u_first, costs, old_costs, alphas, objs, n_ls_iter, info};
-  return launch_mpc_fwd(nx, nu, fa, static_cast<hipStream_t>(stream_));
+  const MpcSearchRoute r = mpc_search_route(search_call(nx, nu, fa));
+  return r.code != 0 ? r.code : r.launch({fa, nx, nu}, static_cast<hipStream_t>(stream_));
 }
 
 int dmpc_mpc_forward_rec_pendulum(int T, int B, const float *Ks, const float *ks, const float *controls,
@@ -762,7 +897,8 @@ int dmpc_mpc_forward_rec_pendulum(int T, int B, const float *Ks, const float *ks
   MpcFwdArgs fa{T, B, Ks, ks, controls, states, u_lower, u_upper, C_true, c_true, nullptr, nullptr, ls_decay,
                 max_ls_iter, /*ls_cap=*/64, x_out, u_out, u_first, costs, old_costs, alphas, objs, n_ls_iter, info,
                 /*dyn_kind=*/1, g, m, l, dt, max_torque};
-  return launch_mpc_fwd(3, 1, fa, static_cast<hipStream_t>(stream_));
+  const MpcSearchRoute r = mpc_search_route(search_call(3, 1, fa));
+  return r.code != 0 ? r.code : r.launch({fa, 3, 1}, static_cast<hipStream_t>(stream_));
 }
 
 int dmpc_pendulum_rollout_linearize(int T, int B, const float *x_init, const float *u, float g, float m, float l,
@@ -806,16 +942,17 @@ int dmpc_mpc_step_forward(int T, int B, int nx, int nu, const float *C_hat, cons
   MpcBackArgs ba{T, B, C_hat, c_use, F_hat, f_use, controls, u_lower, u_upper, n_qp_iter_max, Ks_out, ks_out,
                  n_qp_iter, info, nullptr, batch_coupled ? reinterpret_cast<unsigned *>(base + w.sync) : nullptr,
                  need_expand ? states : nullptr};
-  if (mpc_needs_tiles(nx, nu) || batch_coupled) ba.tiled_scratch = reinterpret_cast<float *>(base + w.tiled);
   MpcFwdArgs fa{T, B, Ks_out, ks_out, controls, states, u_lower, u_upper, C_true, c_true, F_true, f_true, ls_decay,
                 max_ls_iter, /*ls_cap=*/64, x_out, u_out, u_first, costs, old_costs, alphas, objs, n_ls_iter, info};
-  {
-    const int rc = launch_mpc_step_fused(nx, nu, ba, fa, stream);
-    if (rc != DMPC_E_UNSUPPORTED) return rc;
-  }
-  int rc = launch_mpc_back(nx, nu, ba, stream);
-  if (rc != 0) return rc;
-  return launch_mpc_fwd(nx, nu, fa, stream);
+  // both halves are asked before anything is launched (the workspace holds a tiled scratch for whoever reads one)
+  const MpcSweepRoute sweep = mpc_sweep_route(sweep_call(nx, nu, ba, false, true));
+  if (sweep.code != 0) return sweep.code;
+  const MpcSearchRoute search = mpc_search_route(search_call(nx, nu, fa));
+  if (search.code != 0) return search.code;
+  if (sweep.needs_scratch) ba.tiled_scratch = reinterpret_cast<float *>(base + w.tiled);
+  if (const MpcStepLauncher fused = fused_step(sweep, search)) return fused(ba, fa, stream);
+  const int rc = run_sweep(sweep, nx, nu, ba, stream);
+  return rc != 0 ? rc : search.launch({fa, nx, nu}, stream);
 }
 
 int dmpc_lin_rollout(int T, int B, int nx, int nu, const float *x_init, const float *u, const float *F,
@@ -866,6 +1003,7 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   float *xs = fp(w.xs), *c_back = fp(w.c_back), *Ks = fp(w.Ks), *ks = fp(w.ks), *x_new = fp(w.x_new);
   float *u_buf[2] = {fp(w.u_a), fp(w.u_b)};
   float *u1 = fp(w.u1), *costs = fp(w.costs), *alphas = fp(w.alphas);
+  unsigned *sel_sync = reinterpret_cast<unsigned *>(base + w.sel_sync);
   const float *F_hat = dyn_kind == 0 ? F : fp(w.F);
   const float pg = dyn_kind == 1 ? dyn_params[0] : 0.f, pm = dyn_kind == 1 ? dyn_params[1] : 0.f,
               pl = dyn_kind == 1 ? dyn_params[2] : 0.f, pdt = dyn_kind == 1 ? dyn_params[3] : 0.f,
@@ -884,21 +1022,44 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   const bool fuse_lin = dyn_kind == 1 && !knob_on<Knob::DMPC_NO_SPEC_LS>();
   float *x_buf[2] = {xs, x_new};
   const bool copy_here = B <= kDdpCopyHereMaxB && rows * (size_t)(nx + nu) <= kDdpCopyHereMaxElems;
-  bool fused_select = false;   // decided at the first sweep: the bookkeeping of iteration i rides in sweep i + 1's launch
+  // MPCstep.forward with need_expand: f_hat = None                                        mpc_step.py:305-328
+  // pendulum: c_back was re-centred by the rollout kernel / the previous line search; LinDx: the backward sweep
+  // re-centres c itself
+  auto back_args = [&](const float *u_cur, const float *xs_it) {
+    return MpcBackArgs{T, B, C, dyn_kind == 1 ? c_back : c, F_hat, nullptr, u_cur, u_lower, u_upper, n_qp_iter_max, Ks, ks,
+                       ip(w.nqp), info, done, batch_coupled ? reinterpret_cast<unsigned *>(base + w.sync) : nullptr,
+                       dyn_kind == 1 ? nullptr : xs_it, 0};
+  };
+  bool fused_select = false;   // the bookkeeping of iteration i rides in sweep i + 1's launch
+  auto fwd_args = [&](const float *u_cur, float *xs_it, float *xn_it, float *u_new, float *u1_it, float *costs_it) {
+    return MpcFwdArgs{T, B, Ks, ks, u_cur, xs_it, u_lower, u_upper, C, c, dyn_kind == 0 ? F : nullptr,
+                      dyn_kind == 0 ? f : nullptr, ls_decay, max_ls_iter, /*ls_cap=*/64, xn_it, u_new, u1_it, costs_it,
+                      /*old_costs: nobody reads them here*/ nullptr,
+                      alphas, nullptr, ip(w.nls), info, dyn_kind, pg, pm, pl, pdt, pmax, pclosed, done,
+                      fuse_lin ? fp(w.F) : nullptr, fuse_lin ? fp(w.f) : nullptr, fuse_lin ? c_back : nullptr, 0,
+                      fused_select && info != nullptr ? ip(w.info_back) : nullptr};
+  };
+  // Every route the chain takes, asked before its first launch: [0] the first iteration, which reads the caller's controls in
+  // place, [1] the later ones, whose controls are the workspace's.  The bookkeeping rides along (fused_select) when the first
+  // sweep goes through the ring - the pendulum's fused chain alone.
+  MpcSweepRoute sweep[2];
+  MpcSearchRoute search[2];
+  sweep[0] = mpc_sweep_route(sweep_call(nx, nu, back_args(u_init, xs), false, true));
+  fused_select = fuse_lin && copy_here && (sweep[0].kind == MpcKernel::kStream || sweep[0].kind == MpcKernel::kRing);
+  sweep[1] = mpc_sweep_route(sweep_call(nx, nu, back_args(u_buf[1], x_new), fused_select, true));
+  search[0] = mpc_search_route(search_call(nx, nu, fwd_args(u_init, xs, x_new, u_buf[1], u1, costs)));
+  search[1] = mpc_search_route(search_call(nx, nu, fwd_args(u_buf[1], x_new, xs, u_buf[0], u1, costs)));
+  for (const int code : {sweep[0].code, search[0].code, sweep[1].code, search[1].code})
+    if (code != 0) return code;
   DdpSelectArgs sa{};
-  // One launch per iteration (box_ddp_pendulum_iter_kernel) when the fused chain runs and the search is the wavefront-per-
-  // trajectory one: the search then runs BESIDE the previous iteration's bookkeeping, so what that reads (the controls the
+  // One launch per iteration (box_ddp_pendulum_iter_kernel) when the fused chain runs on the generated sweep and the search is
+  // the wavefront-per-trajectory one: the search then runs BESIDE the previous iteration's bookkeeping, so what that reads (the controls the
   // step started from, the first pass's controls, the costs) must not be what this search writes - three control buffers in
   // rotation, two of u_first / costs, and the iteration's flags through a staging word that the bookkeeping merges.
   // The first of these launches also rolls out and linearises the nominal trajectory (the chain's first launch otherwise).
   // DMPC_NO_DDP_ITER_FUSED=1 (read at every call): rollout, sweep and search as launches of their own (A/B timing; bit-identical).
-  bool iter_fused = false;
-  if (fuse_lin && nx == 3 && nu == 1 && copy_here) {   // (decided before the first launch: the first iteration's launch also rolls out)
-    const MpcBackArgs ba0{T, B, C, c_back, F_hat, nullptr, u_init, u_lower, u_upper, n_qp_iter_max, Ks, ks, ip(w.nqp), info, done,
-                          batch_coupled ? reinterpret_cast<unsigned *>(base + w.sync) : nullptr, nullptr, 0};
-    iter_fused = mpc_back_dma_ok(ba0) && T >= 2 && T <= kSpec4MaxT && !knob_on<Knob::DMPC_NO_SPEC4>() &&
-                 !knob_on<Knob::DMPC_NO_MPC_ASM>() && aligned16(fp(w.F)) && !knob_on_now<Knob::DMPC_NO_DDP_ITER_FUSED>();
-  }
+  const bool iter_fused = fuse_lin && copy_here && sweep[0].kind == MpcKernel::kStream && search[0].kind == MpcKernel::kSpec4 &&
+                          aligned16(fp(w.F)) && !knob_on_now<Knob::DMPC_NO_DDP_ITER_FUSED>();
   float *u_buf3[3] = {fp(w.u_a), fp(w.u_b), fp(w.u_c)};
   float *u1_2[2] = {u1, fp(w.u1_b)}, *costs_2[2] = {costs, fp(w.costs_b)};
   int32_t *stage_2[2] = {ip(w.stage_a), ip(w.stage_b)};
@@ -909,6 +1070,7 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
     float *u1_it = iter_fused ? u1_2[it & 1] : u1, *costs_it = iter_fused ? costs_2[it & 1] : costs;
     float *xs_it = fuse_lin ? x_buf[it & 1] : xs;
     float *xn_it = fuse_lin ? x_buf[(it & 1) ^ 1] : x_new;
+    const int k = it == 0 ? 0 : 1;
     // nominal trajectory and the Taylor models around it                                    box_ddp.py:123-171
     PendulumArgs pa_first{};     // one-launch iterations: the first iteration's launch rolls out and linearises itself (pa_first.T > 0)
     if (dyn_kind == 1) {
@@ -922,24 +1084,13 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
       DMPC_LAUNCH_GGL(lin_rollout_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, T, B, nx, nu, x_init, u_cur, F,
                          f, xs_it, it == 0 ? nullptr : done, it == 0 ? clear : ChainClear{});
     }
-    // MPCstep.forward with need_expand: f_hat = None                                        mpc_step.py:305-328
-    // pendulum: c_back was re-centred by the rollout kernel / the previous line search; LinDx: the backward sweep
-    // re-centres c itself
-    MpcBackArgs ba{T, B, C, dyn_kind == 1 ? c_back : c, F_hat, nullptr, u_cur, u_lower, u_upper, n_qp_iter_max, Ks, ks,
-                   ip(w.nqp), info, done, batch_coupled ? reinterpret_cast<unsigned *>(base + w.sync) : nullptr,
-                   dyn_kind == 1 ? nullptr : xs_it, 0};
-    if (mpc_needs_tiles(nx, nu) || batch_coupled) ba.tiled_scratch = fp(w.tiled);
-    if (it == 0) fused_select = fuse_lin && nx == 3 && nu == 1 && copy_here && mpc_back_dma_ok(ba);
+    MpcBackArgs ba = back_args(u_cur, xs_it);
+    if (sweep[k].needs_scratch) ba.tiled_scratch = fp(w.tiled);
     if (fused_select && info != nullptr) {   // the sweep may run ahead of `done`: its flags count only if the search follows
       ba.info = ip(w.info_back);
       ba.info_store = 1;
     }
-    MpcFwdArgs fa{T, B, Ks, ks, u_cur, xs_it, u_lower, u_upper, C, c, dyn_kind == 0 ? F : nullptr,
-                  dyn_kind == 0 ? f : nullptr, ls_decay, max_ls_iter, /*ls_cap=*/64, xn_it, u_new, u1_it, costs_it,
-                  /*old_costs: nobody reads them here*/ nullptr,
-                  alphas, nullptr, ip(w.nls), info, dyn_kind, pg, pm, pl, pdt, pmax, pclosed, done,
-                  fuse_lin ? fp(w.F) : nullptr, fuse_lin ? fp(w.f) : nullptr, fuse_lin ? c_back : nullptr, 0,
-                  fused_select && info != nullptr ? ip(w.info_back) : nullptr};
+    MpcFwdArgs fa = fwd_args(u_cur, xs_it, xn_it, u_new, u1_it, costs_it);
     int rc;
     if (iter_fused) {
       if (info != nullptr) {     // the search may run ahead of `done` too: sweep + search flags to this iteration's staging word
@@ -949,15 +1100,14 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
       if (it == 0) ba.done = fa.done = nullptr;   // (this launch clears the flag; nothing can have stopped the loop yet)
       const int n_sel = it > 0 ? select_parts(B) : 0;
       const size_t lds = std::max(mpc_asm_lds_bytes<3, 1>(), Spec4Layout::lds_bytes(T));
-      DMPC_LAUNCH_GGL(box_ddp_pendulum_iter_kernel, dim3(B / 4 + n_sel), dim3(256), lds, stream, ba, fa, sa, n_sel,
-                      reinterpret_cast<unsigned *>(base + w.sel_sync), pa_first);
+      DMPC_LAUNCH_GGL(box_ddp_pendulum_iter_kernel, dim3(B / 4 + n_sel), dim3(256), lds, stream, ba, fa, sa, n_sel, sel_sync,
+                      pa_first);
       rc = (int)hipGetLastError();
       if (rc != 0) return rc;
     } else {
-      rc = launch_mpc_back(nx, nu, ba, stream, fused_select && it > 0 ? &sa : nullptr,
-                           reinterpret_cast<unsigned *>(base + w.sel_sync));
+      rc = run_sweep(sweep[k], nx, nu, ba, stream, fused_select && it > 0 ? &sa : nullptr, sel_sync);
       if (rc != 0) return rc;
-      rc = launch_mpc_fwd(nx, nu, fa, stream);
+      rc = search[k].launch({fa, nx, nu}, stream);
       if (rc != 0) return rc;
     }
     // best-so-far update and stop tests of this iteration                                   box_ddp.py:200-230
@@ -981,8 +1131,7 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   // launch splits it
   const bool split_last = fused_select && select_parts(B) > 1;
   if (split_last)
-    DMPC_LAUNCH_GGL((box_ddp_select_parts_kernel<3, 1>), dim3(select_parts(B)), dim3(256), 0, stream, sa,
-                       reinterpret_cast<unsigned *>(base + w.sel_sync));
+    DMPC_LAUNCH_GGL((box_ddp_select_parts_kernel<3, 1>), dim3(select_parts(B)), dim3(256), 0, stream, sa, sel_sync);
   DMPC_LAUNCH_GGL(box_ddp_summary_kernel, dim3(1), dim3(1024), 0, stream, rows * nu, B, u_init, u_lower, u_upper, info,
                      (int)DMPC_INFO_NONFINITE, du_norm_best, eps, state, sa, fused_select && !split_last ? 1 : 0);
   return (int)hipGetLastError();

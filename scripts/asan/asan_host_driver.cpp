@@ -53,6 +53,37 @@ int main() {
                                       ws, dmpc_mpc_step_workspace_bytes(T, B, nx, nu), pi, nullptr);
           (void)dmpc_lqr_solve_f64(T, B, nx, nu, pd, pd, pd, pd, pd, nullptr, nullptr, nullptr, pd, pd, ws,
                                    dmpc_lqr_f64_workspace_bytes(T, B, nx, nu), pi, nullptr);
+          // the MPC step family's routes and launchers (csrc/mpc_api.hip): the halves of the step on their own, the box QP, the
+          // device-driven BoxDDP loop; `controls` aligned and four bytes off, per-trajectory and batch-coupled
+          float *p4 = reinterpret_cast<float *>(0x1004);
+          (void)dmpc_mpc_step_forward(T, B, nx, nu, p, p, p, p, p4, p, p, p, p, p, p, p, 0, 0.2f, 5, 20, 1, p, p, p, p, p, p, p, p, p, pi, pi,
+                                      ws, dmpc_mpc_step_workspace_bytes(T, B, nx, nu), pi, nullptr);
+          for (int coupled : {0, 1}) {
+            const size_t bwb = dmpc_mpc_backward_rec_workspace_bytes(T, B, nx, nu, 20, coupled);
+            for (float *u : {p, p4}) {
+              (void)dmpc_mpc_backward_rec(T, B, nx, nu, p, p, p, p, u, p, p, 20, coupled, p, p, pi, ws, bwb, pi, nullptr);
+              (void)dmpc_mpc_backward_rec(T, B, nx, nu, p, p, p, nullptr, u, p, p, 20, coupled, p, p, pi, ws, bwb, pi, nullptr);
+            }
+            if (bwb > 0)
+              EXPECT(dmpc_mpc_backward_rec(T, B, nx, nu, p, p, p, p, p, p, p, 20, coupled, p, p, pi, ws, bwb - 1, pi, nullptr) == DMPC_E_WORKSPACE);
+            (void)dmpc_pnqp(B, nu, p, p, p, p, nullptr, 20, coupled, p, p, pi, p, pi, ws, dmpc_pnqp_workspace_bytes(B, nu, 20, coupled), pi,
+                            nullptr);
+            const float pendulum[6] = {10.f, 1.f, 1.f, 0.05f, 2.f, 0.f};
+            const size_t dwb = dmpc_box_ddp_workspace_bytes(T, B, nx, nu);
+            for (float *u : {p, p4}) {
+              (void)dmpc_box_ddp(T, B, nx, nu, p, p, p, p, p, 0, nullptr, u, p, p, 1e-3f, 5, 0.2f, 10, 1e-3f, 3, 20, 0, coupled, p, p, p, p, p,
+                                 pi, ws, dwb, pi, nullptr);
+              const int rd = dmpc_box_ddp(T, B, nx, nu, p, p, p, nullptr, nullptr, 1, pendulum, u, p, p, 1e-3f, 5, 0.2f, 10, 1e-3f, 3, 20, 0,
+                                          coupled, p, p, p, p, p, pi, ws, dwb, pi, nullptr);
+              if (nx != 3 || nu != 1) EXPECT(rd == DMPC_E_BADARG);
+            }
+          }
+          for (float *u : {p, p4})
+            (void)dmpc_mpc_forward_rec(T, B, nx, nu, p, p, u, p, p, p, p, p, p, p, 0.2f, 5, p, p, p, p, p, p, p, pi, pi, nullptr);
+          if (nx == 3 && nu == 1)
+            for (float *u : {p, p4})
+              (void)dmpc_mpc_forward_rec_pendulum(T, B, p, p, u, p, p, p, p, p, 10.f, 1.f, 1.f, 0.05f, 2.f, 0.2f, 5, p, p, p, p, p, p, p, pi,
+                                                  pi, nullptr);
         }
         // inconsistent arguments are refused before anything else happens
         EXPECT(dmpc_lqr_solve(T, B, nx, nu, nullptr, p, p, p, p, nullptr, nullptr, nullptr, p, p, ws, wsb, pi, nullptr) == DMPC_E_BADARG);
