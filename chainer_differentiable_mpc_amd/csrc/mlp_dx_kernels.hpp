@@ -35,7 +35,7 @@
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
-// bound_tol, is_finite, wave_sum64 and MpcFwdArgs come from the MPC step's headers.  Those headers also define the
+// line_search.hpp's pieces, is_finite and wave_sum64 come from the MPC step's headers.  Those headers also define the
 // non-template kernels of mpc_api.hip's translation unit; here their functions get internal linkage, so this translation
 // unit neither defines those kernels a second time nor emits the ones it does not launch.
 #pragma clang attribute push(__attribute__((internal_linkage)), apply_to = function)
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(c
 }
 
 // forward_rec: the arithmetic of a pass, its order and the search's decisions are mpc_generic_forward_kernel's (and
-// through it mpc_forward_rec_kernel's): the cost difference per timestep without cancellation, bound_tol's snap, the
+// through it mpc_forward_rec_kernel's): the cost difference per timestep without cancellation, box_clamp's snap, the
 // pass cap.  a.F / a.f are not read.  The loop is wave-uniform by construction - a wavefront is one trajectory - so a
 // trajectory that has finished runs, stores and commits nothing more.
 template <int ACT>
@@ -248,10 +248,11 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(con
   const int lx = is_x ? lane : 0;
   const int lt = lane < ns ? lane : 0;
 
-  float alpha = 1.0f, cost = 0.f, old_cost = 0.f;
-  int n_pass = 0;
-  bool worse = true;
-  while (worse && n_pass < a.ls_cap) {                                                   // mpc_step.py:196
+  float cost = 0.f, old_cost = 0.f;
+  LineSearch ls;
+  while (ls.searching(a.ls_cap)) {
+    const float alpha = ls.alpha;
+    const bool first = ls.n_pass == 0;
     float xc = is_x ? a.states[(size_t)b * nx + lane] : 0.f;                             // :198
     cost = 0.f;
     float delta = 0.f;   // current_cost - OLD_COST, per timestep and without cancellation (see mpc_forward_rec_kernel)
@@ -264,15 +265,12 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(con
       float v = alpha * a.ks[tb * nu + mu];
       for (int i = 0; i < nx; ++i) v = fmaf(Kr[i], lane_value(dx, i), v);
       v += u0;                                                                           // :209-219
-      const float lb = a.lower[tb * nu + mu], ub = a.upper[tb * nu + mu];
-      v = fminf(fmaxf(v, lb), ub);                                                       // :221
-      v = (v - lb <= bound_tol(lb)) ? lb : v;
-      v = (ub - v <= bound_tol(ub)) ? ub : v;
+      v = box_clamp(v, a.lower[tb * nu + mu], a.upper[tb * nu + mu]);
       const float tau = is_x ? xc : (is_u ? v : 0.f);
       const float tau0 = is_x ? x0 : (is_u ? u0 : 0.f);
       if (is_u) {
         a.u[tb * nu + mu] = v;
-        if (a.u_first != nullptr && n_pass == 0) a.u_first[tb * nu + mu] = v;            // :260-263
+        if (a.u_first != nullptr && first) a.u_first[tb * nu + mu] = v;                  // :260-263
       }
       if (is_x) a.x[tb * nx + lane] = xc;
       float part = 0.f, part0 = 0.f, partd = 0.f;                                        // :246-251, util.py:162-198
@@ -289,38 +287,26 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(con
         const float ci = a.c[tb * ns + lt];
         const float di = tau - tau0;
         if (lane < ns) {
-          part = tau * fmaf(0.5f, qi, ci);
-          part0 = tau0 * fmaf(0.5f, q0, ci);
-          partd = fmaf(di, fmaf(0.5f, qi, ci), 0.5f * tau0 * qd);
+          part = cost_row(tau, qi, ci);
+          part0 = cost_row(tau0, q0, ci);
+          partd = cost_row_diff(di, qi, ci, tau0, qd);
         }
       }
       const float obj = wave_sum64(part);
       cost += obj;
       delta += wave_sum64(partd);
-      if (n_pass == 0) old_cost += wave_sum64(part0);                                    // :191
+      if (first) old_cost += wave_sum64(part0);                                          // :191
       if (a.objs != nullptr && lane == 0) a.objs[tb] = obj;
       if (t < T - 1) {                                                                   // :237-240
         float act[kMlpUnits], dact[kMlpUnits];
         xc = mlp_next<ACT>(m, L, lane, tau, act, dact);
       }
     }
-    ++n_pass;
-    worse = delta > 0.f;                 // :266  current_cost > OLD_COST
-    if (worse) alpha *= a.ls_decay;      // :268
+    ls.advance(delta, a.ls_decay);
   }
-  int info_bits = 0;
-  if (worse) {                           // cap hit: the reference would still be looping; :274
-    alpha /= a.ls_decay;
-    info_bits |= 8;
-  }
-  if (!is_finite(cost)) info_bits |= 2;
-  if (lane == 0) {
-    a.costs[b] = cost;
-    if (a.old_costs != nullptr) a.old_costs[b] = old_cost;
-    a.alphas[b] = alpha;
-    a.n_ls[b] = n_pass;
-    if (a.info != nullptr && info_bits != 0) atomicOr(&a.info[b], info_bits);
-  }
+  if (ls.worse) ls.alpha = cap_alpha_sequential(ls.alpha, a.ls_decay);
+  // info_in, info_store: dmpc_mpc_forward_rec_mlp has neither (its MpcFwdArgs leaves both zero)
+  if (lane == 0) search_store<false, false>(a, b, cost, old_cost, ls.alpha, ls.n_pass, search_flags(ls.worse, cost));
 }
 
 // The gradient of L(f) with respect to W1, b1, W2, b2 for f_t = next(x_t, u_t) - F_t [x_t;u_t] along the rolled states,

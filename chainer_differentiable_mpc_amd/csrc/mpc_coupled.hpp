@@ -78,7 +78,7 @@ __global__ __launch_bounds__(kTiledThreads) void pnqp_coupled_kernel(const PnqpT
     }
     if (tid == 0) {
       a.n_iter_out[b] = o.it;
-      if (!o.converged && a.info != nullptr) atomicOr(&a.info[b], 4);     // DMPC_INFO_QP_ITERCAP
+      if (!o.converged && a.info != nullptr) atomicOr(&a.info[b], DMPC_INFO_QP_ITERCAP);
     }
   }
 }

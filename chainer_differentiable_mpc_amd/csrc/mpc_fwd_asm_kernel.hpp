@@ -101,18 +101,11 @@ __device__ __forceinline__ void mpc_forward_asm_body(const MpcFwdArgs &a, const 
   int nls, worse;
   G::run(in, cost, oldc, alpha, nls, worse);
 
+  // info_in, info_store: the dispatch hands neither to this kernel (mpc_search_route: both go to the pendulum's speculative
+  // searches alone)
   if (lane == 0) {
-    int info_bits = 0;
-    if (worse) {                           // cap hit: the reference would still be looping; :274
-      alpha /= a.ls_decay;
-      info_bits |= 8;
-    }
-    if (!is_finite(cost)) info_bits |= 2;
-    a.costs[b] = cost;
-    if (a.old_costs != nullptr) a.old_costs[b] = oldc;
-    a.alphas[b] = alpha;
-    a.n_ls[b] = nls;
-    if (a.info != nullptr && info_bits != 0) atomicOr(&a.info[b], info_bits);
+    if (worse) alpha = cap_alpha_sequential(alpha, a.ls_decay);
+    search_store<false, false>(a, b, cost, oldc, alpha, nls, search_flags(worse != 0, cost));
   }
 }
 

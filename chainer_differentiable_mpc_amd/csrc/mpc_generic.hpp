@@ -197,31 +197,28 @@ __global__ __launch_bounds__(64) void mpc_generic_forward_kernel(const MpcFwdArg
   float *tau = xh + nx;    // [ns]  [new_x_t ; new_u_t]
   float *tau0 = tau + ns;  // [ns]  the iterate the step started from
 
-  float alpha = 1.0f, cost = 0.f, old_cost = 0.f;
-  int n_pass = 0;
-  bool worse = true;
-  while (worse && n_pass < a.ls_cap) {                                                   // mpc_step.py:196
+  float cost = 0.f, old_cost = 0.f;
+  LineSearch ls;
+  while (ls.searching(a.ls_cap)) {
     if (lane < nx) xh[lane] = a.states[(size_t)b * nx + lane];                           // :198
     __syncthreads();
     cost = 0.f;
-    float delta = 0.f;   // current_cost - OLD_COST, per timestep and without cancellation (see mpc_forward_rec_kernel)
+    float delta = 0.f;   // current_cost - OLD_COST, per timestep and without cancellation (line_search.hpp)
     for (int t = 0; t < T; ++t) {
       const size_t tb = (size_t)t * B + b;
       if (lane < nu) {
         const int m = lane;
         const float *Kr = a.Ks + (tb * nu + m) * nx;
-        float v = alpha * a.ks[tb * nu + m];
+        float v = ls.alpha * a.ks[tb * nu + m];
 #pragma unroll 8
         for (int i = 0; i < nx; ++i) v = fmaf(Kr[i], xh[i] - a.states[tb * nx + i], v);
         v += a.controls[tb * nu + m];                                                    // :209-219
         const float lb = a.lower[tb * nu + m], ub = a.upper[tb * nu + m];
-        v = fminf(fmaxf(v, lb), ub);                                                     // :221
-        v = (v - lb <= bound_tol(lb)) ? lb : v;
-        v = (ub - v <= bound_tol(ub)) ? ub : v;
+        v = box_clamp(v, lb, ub);
         tau[nx + m] = v;
         tau0[nx + m] = a.controls[tb * nu + m];
         a.u[tb * nu + m] = v;
-        if (a.u_first != nullptr && n_pass == 0) a.u_first[tb * nu + m] = v;             // :260-263
+        if (a.u_first != nullptr && ls.n_pass == 0) a.u_first[tb * nu + m] = v;          // :260-263
       }
       if (lane < nx) {
         tau[lane] = xh[lane];
@@ -242,14 +239,14 @@ __global__ __launch_bounds__(64) void mpc_generic_forward_kernel(const MpcFwdArg
         }
         const float ci = a.c[tb * ns + lane];
         const float di = tau[lane] - tau0[lane];
-        part = tau[lane] * fmaf(0.5f, qi, ci);
-        part0 = tau0[lane] * fmaf(0.5f, q0, ci);
-        partd = fmaf(di, fmaf(0.5f, qi, ci), 0.5f * tau0[lane] * qd);
+        part = cost_row(tau[lane], qi, ci);
+        part0 = cost_row(tau0[lane], q0, ci);
+        partd = cost_row_diff(di, qi, ci, tau0[lane], qd);
       }
       const float obj = wave_sum64(part);
       cost += obj;
       delta += wave_sum64(partd);
-      if (n_pass == 0) old_cost += wave_sum64(part0);                                    // :191
+      if (ls.n_pass == 0) old_cost += wave_sum64(part0);                                 // :191
       if (a.objs != nullptr && lane == 0) a.objs[tb] = obj;
       float xn = 0.f;
       if (lane < nx && t < T - 1) {                                                      // :229-236
@@ -262,23 +259,12 @@ __global__ __launch_bounds__(64) void mpc_generic_forward_kernel(const MpcFwdArg
       if (lane < nx && t < T - 1) xh[lane] = xn;
       __syncthreads();
     }
-    ++n_pass;
-    worse = delta > 0.f;                 // :266  current_cost > OLD_COST
-    if (worse) alpha *= a.ls_decay;      // :268
+    ls.advance(delta, a.ls_decay);
   }
-  int info_bits = 0;
-  if (worse) {                           // cap hit: the reference would still be looping; :274
-    alpha /= a.ls_decay;
-    info_bits |= 8;
-  }
-  if (!is_finite(cost)) info_bits |= 2;
-  if (lane == 0) {
-    a.costs[b] = cost;
-    if (a.old_costs != nullptr) a.old_costs[b] = old_cost;
-    a.alphas[b] = alpha;
-    a.n_ls[b] = n_pass;
-    if (a.info != nullptr && info_bits != 0) atomicOr(&a.info[b], info_bits);
-  }
+  if (ls.worse) ls.alpha = cap_alpha_sequential(ls.alpha, a.ls_decay);
+  // info_in, info_store: the dispatch hands neither to this kernel (mpc_search_route: both go to the pendulum's speculative
+  // searches alone)
+  if (lane == 0) search_store<false, false>(a, b, cost, old_cost, ls.alpha, ls.n_pass, search_flags(ls.worse, cost));
 }
 
 // ---- the same forward pass with its inputs staged through LDS (round 4).  mpc_generic_forward_kernel reads a row of C, F and K
@@ -333,14 +319,13 @@ __global__ __launch_bounds__(64) void mpc_staged_forward_kernel(const MpcFwdArgs
     dma_run_floats(a.states + tb * nx, dst + L.x * 4, nx, lane);
   };
 
-  float alpha = 1.0f, cost = 0.f, old_cost = 0.f;
-  int n_pass = 0;
-  bool worse = true;
-  while (worse && n_pass < a.ls_cap) {                                                   // mpc_step.py:196
+  float cost = 0.f, old_cost = 0.f;
+  LineSearch ls;
+  while (ls.searching(a.ls_cap)) {
     issue(0, 0);
     if (lane < nx) xh[lane] = a.states[(size_t)b * nx + lane];                           // :198
     cost = 0.f;
-    float delta = 0.f;   // current_cost - OLD_COST, per timestep and without cancellation (see mpc_forward_rec_kernel)
+    float delta = 0.f;   // current_cost - OLD_COST, per timestep and without cancellation (line_search.hpp)
     for (int t = 0; t < T; ++t) {
       const size_t tb = (size_t)t * B + b;
       // the slot of this step has landed (requested a step ago), the other one has been read: it takes the next step's
@@ -351,19 +336,17 @@ __global__ __launch_bounds__(64) void mpc_staged_forward_kernel(const MpcFwdArgs
       if (lane < nu) {
         const int m = lane;
         const float *Kr = S + L.K + m * nx;
-        float v = alpha * S[L.k + m];
+        float v = ls.alpha * S[L.k + m];
 #pragma unroll 8
         for (int i = 0; i < nx; ++i) v = fmaf(Kr[i], xh[i] - S[L.x + i], v);
         const float u0 = S[L.u + m];
         v += u0;                                                                         // :209-219
         const float lb = S[L.lo + m], ub = S[L.hi + m];
-        v = fminf(fmaxf(v, lb), ub);                                                     // :221
-        v = (v - lb <= bound_tol(lb)) ? lb : v;
-        v = (ub - v <= bound_tol(ub)) ? ub : v;
+        v = box_clamp(v, lb, ub);
         tau[nx + m] = v;
         tau0[nx + m] = u0;
         a.u[tb * nu + m] = v;
-        if (a.u_first != nullptr && n_pass == 0) a.u_first[tb * nu + m] = v;             // :260-263
+        if (a.u_first != nullptr && ls.n_pass == 0) a.u_first[tb * nu + m] = v;          // :260-263
       }
       if (lane < nx) {
         const float xl = xh[lane];
@@ -385,14 +368,14 @@ __global__ __launch_bounds__(64) void mpc_staged_forward_kernel(const MpcFwdArgs
         }
         const float ci = S[L.c + lane];
         const float di = tau[lane] - tau0[lane];
-        part = tau[lane] * fmaf(0.5f, qi, ci);
-        part0 = tau0[lane] * fmaf(0.5f, q0, ci);
-        partd = fmaf(di, fmaf(0.5f, qi, ci), 0.5f * tau0[lane] * qd);
+        part = cost_row(tau[lane], qi, ci);
+        part0 = cost_row(tau0[lane], q0, ci);
+        partd = cost_row_diff(di, qi, ci, tau0[lane], qd);
       }
       const float obj = wave_sum64(part);
       cost += obj;
       delta += wave_sum64(partd);
-      if (n_pass == 0) old_cost += wave_sum64(part0);                                    // :191
+      if (ls.n_pass == 0) old_cost += wave_sum64(part0);                                 // :191
       if (a.objs != nullptr && lane == 0) a.objs[tb] = obj;
       float xn = 0.f;
       if (lane < nx && t < T - 1) {                                                      // :229-236
@@ -404,25 +387,14 @@ __global__ __launch_bounds__(64) void mpc_staged_forward_kernel(const MpcFwdArgs
       __syncthreads();
       if (lane < nx && t < T - 1) xh[lane] = xn;
     }
-    ++n_pass;
-    worse = delta > 0.f;                 // :266  current_cost > OLD_COST
-    if (worse) alpha *= a.ls_decay;      // :268
+    ls.advance(delta, a.ls_decay);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();                     // (the next pass refills slot 0 and rewrites xh)
   }
-  int info_bits = 0;
-  if (worse) {                           // cap hit: the reference would still be looping; :274
-    alpha /= a.ls_decay;
-    info_bits |= 8;
-  }
-  if (!is_finite(cost)) info_bits |= 2;
-  if (lane == 0) {
-    a.costs[b] = cost;
-    if (a.old_costs != nullptr) a.old_costs[b] = old_cost;
-    a.alphas[b] = alpha;
-    a.n_ls[b] = n_pass;
-    if (a.info != nullptr && info_bits != 0) atomicOr(&a.info[b], info_bits);
-  }
+  if (ls.worse) ls.alpha = cap_alpha_sequential(ls.alpha, a.ls_decay);
+  // info_in, info_store: the dispatch hands neither to this kernel (mpc_search_route: both go to the pendulum's speculative
+  // searches alone)
+  if (lane == 0) search_store<false, false>(a, b, cost, old_cost, ls.alpha, ls.n_pass, search_flags(ls.worse, cost));
 }
 
 }  // namespace dmpc

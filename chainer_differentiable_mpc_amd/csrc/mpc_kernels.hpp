@@ -14,18 +14,13 @@
 #include "colwise.hpp"
 #include "dma_gather.hpp"
 #include "dpp_blocks_gen.hpp"
+#include "line_search.hpp"
 #include "lqr_dma_kernel.hpp"
 #include "lqr_kernels.hpp"
 #include "pnqp_device.hpp"
 #include "riccati_blocks.hpp"
 
 namespace dmpc {
-
-// "Sits on its bound": the reference tests |u - bound| <= 1e-8 in float64 (mpc_step.py:363-364), where a
-// clamped control differs from its bound by at most an ulp (1e-16).  In float32 an ulp at |bound| ~ 1 is
-// 6e-8, so the same test needs a tolerance of a few float32 ulps; controls that close are also snapped
-// onto the bound by the rollout so that `u == bound` holds exactly for callers.
-__device__ __forceinline__ float bound_tol(float bound) { return 1e-8f + 4.0f * 1.1920929e-07f * fmaxf(1.0f, fabsf(bound)); }
 
 struct MpcBackArgs {
   int T, B;
@@ -374,39 +369,6 @@ __device__ __forceinline__ void pendulum_jacobian_store(const PendulumModel &p, 
   }
 }
 
-struct MpcFwdArgs {
-  int T, B;
-  const float *Ks, *ks;                  // gains from backward_rec
-  const float *controls, *states;        // current iterate  [T,B,nu], [T,B,nx]
-  const float *lower, *upper;            // absolute control bounds [T,B,nu]
-  const float *C, *c, *F, *f;            // TRUE QuadCost / LinDx (f may be nullptr)
-  float ls_decay;
-  int max_ls_iter;                       // only guards the first pass in the reference (:196), kept for the record
-  int ls_cap;                            // safety cap on line-search passes (the reference loop is unbounded)
-  float *x, *u;                          // new trajectory
-  float *u_first;                        // controls of the first (alpha = 1) pass, or nullptr      (:260-263)
-  float *costs, *old_costs, *alphas;     // [B]
-  float *objs;                           // [T,B] per-step cost of the accepted pass, or nullptr
-  int32_t *n_ls;                         // [B] passes run
-  int32_t *info;
-  // TRUE dynamics other than LinDx, evaluated inside the line search (mpc_step.py:237-240 calls a Python callable):
-  //   0 LinDx (F, f above)   1 the pendulum of env_dx/pendulum.py:65-102, simple model (nx = 3, nu = 1)
-  int dyn_kind;
-  float pend_g, pend_m, pend_l, pend_dt, pend_max_torque;
-  int pend_clamp_closed;                 // derivative of the torque clamp at its limits (PendulumModel::clamp_grad)
-  const int32_t *done;                   // device flag of the BoxDDP loop: non-zero -> no-op
-  // The accepted trajectory IS the next iLQR iteration's nominal one (BoxDDP re-rolls it with get_traj and linearises
-  // it, mpc/box_ddp.py:123-136): the speculative pendulum search can write that model while it writes the
-  // trajectory - F_next [T-1,B,3,4], f_next [T-1,B,3], c_next [T,B,4] = C tau + c (mpc_step.py:305-317); nullptr = no.
-  float *F_next, *f_next, *c_next;
-  // speculative search: every candidate keeps its trajectory in LDS (T * 4 floats per lane, T * 4 KB per workgroup)
-  // and the accepted one is copied out instead of being rolled out a second time; 0 = no such buffer was given
-  int traj_in_lds;
-  const int32_t *info_in;                // [B] flags to merge into info (the backward sweep's, when it ran ahead of `done`)
-  int nx_log = 0, nu_log = 0;            // container launches (PAD): the problem's own dimensions
-  int info_store = 0;                    // != 0: info[b] = this search's flags (plain store; pendulum spec4 search only)
-};
-
 // chunks of one wave-step of the forward kernel's LDS-DMA ring (DMA variant):
 // [C | c | F | f | Ks | ks | u | lower | upper | x], four trajectories each
 template <int NX, int NU>
@@ -457,12 +419,8 @@ __global__ __launch_bounds__(256) void mpc_forward_rec_kernel(const MpcFwdArgs a
   const int lane_x = is_x ? lane : nx - 1;
   const int lane_t = PAD ? (lrow >= 0 ? lrow : ns - 1) : (is_tau ? lane : NS - 1);
 
-  // OLD_COST of (states, controls) (mpc_step.py:191) is accumulated during the first pass from the same rows of C.
-  // The test `current_cost > OLD_COST` (:196,266) is NOT taken on the two rounded totals: near a fixed point their
-  // difference is far below float32's resolution of the totals (the reference decides it in float64).  Per timestep
-  //     obj(tau') - obj(tau) = 1/2 d'(C tau') + 1/2 tau'(C d) + c'd ,   d = tau' - tau
-  // is exact algebra for any (also non-symmetric) C and has no cancellation: its rounding error scales with |d|, not
-  // with the cost.  A candidate that has collapsed onto the nominal trajectory gives d = 0, hence exactly 0.
+  // OLD_COST of (states, controls) (mpc_step.py:191) is accumulated during the first pass from the same rows of C; the
+  // test `current_cost > OLD_COST` is taken on the per-timestep difference (line_search.hpp: cost_row_diff).
   float old_cost = 0.f;
 
   // Inputs of one timestep of a pass.  Register-bank variant: the loads of step t+2 are issued before step t is
@@ -602,12 +560,11 @@ __global__ __launch_bounds__(256) void mpc_forward_rec_kernel(const MpcFwdArgs a
     return q;
   };
 
-  float alpha = 1.0f;
+  LineSearch ls;
   float cost = 0.f;
-  int n_pass = 0;
-  bool worse = true;
-  bool searching = a.ls_cap > 0;   // this trajectory's search goes on                      :196
+  bool searching = ls.searching(a.ls_cap);   // this trajectory's search goes on
   for (int pass_idx = 0; __any(searching); ++pass_idx) {
+    const float alpha = ls.alpha;
     float xh = 0.f;                                            // new_x[0] = states[0]     :198
     if constexpr (!DMA) xh = is_x ? a.states[(size_t)b * nx + lane] : 0.f;   // (DMA: from the ring's first slot, below)
     float cost_p = 0.f, old_p = 0.f;
@@ -637,11 +594,8 @@ __global__ __launch_bounds__(256) void mpc_forward_rec_kernel(const MpcFwdArgs a
       float un[NU];
 #pragma unroll
       for (int m = 0; m < NU; ++m) {
-        float v = group_sum<L>(k_lane ? sl.kv[m] * z : 0.f) + sl.uc[m];               // :209-219
-        const float lb = sl.lb[m], ub = sl.ub[m];
-        v = fminf(fmaxf(v, lb), ub);                                                  // :221
-        v = (v - lb <= bound_tol(lb)) ? lb : v;
-        un[m] = (ub - v <= bound_tol(ub)) ? ub : v;
+        const float v = group_sum<L>(k_lane ? sl.kv[m] * z : 0.f) + sl.uc[m];         // :209-219
+        un[m] = box_clamp(v, sl.lb[m], sl.ub[m]);
       }
       float tau = xh;  // [new_x_t ; new_u_t], element per lane
 #pragma unroll
@@ -653,11 +607,10 @@ __global__ __launch_bounds__(256) void mpc_forward_rec_kernel(const MpcFwdArgs a
       const float qi = row_dot(sl, tau), qd = row_dot(sl, dt_);
       // per-lane partial sums over the timesteps; the lanes of the group are added up ONCE after the pass (only the
       // optional per-step output `objs` needs the sum of a single step)                          :246-251, util.py:162-198
-      const float obj_l = is_tau ? tau * fmaf(0.5f, qi, sl.ci) : 0.f;
+      const float obj_l = is_tau ? cost_row(tau, qi, sl.ci) : 0.f;
       cost_p += obj_l;
-      delta += is_tau ? fmaf(dt_, fmaf(0.5f, qi, sl.ci), 0.5f * tau0 * qd) : 0.f;
-      if (pass_idx == 0)   // cost of the iterate, from C tau = C tau' - C d                                 :191
-        old_p += is_tau ? tau0 * fmaf(0.5f, qi - qd, sl.ci) : 0.f;
+      delta += is_tau ? cost_row_diff(dt_, qi, sl.ci, tau0, qd) : 0.f;
+      if (pass_idx == 0) old_p += is_tau ? cost_row_iterate(tau0, qi, qd, sl.ci) : 0.f;                    // :191
       float obj = 0.f;
       if (a.objs != nullptr) obj = group_sum<L>(obj_l);
       if (live && searching) {  // outputs are overwritten by later passes; the last one is the accepted one
@@ -735,25 +688,14 @@ __global__ __launch_bounds__(256) void mpc_forward_rec_kernel(const MpcFwdArgs a
     if (pass_idx == 0) old_cost = group_sum<L>(old_p);
     if (searching) {
       cost = cost_p;
-      ++n_pass;
-      worse = delta > 0.f;                 // :266  current_cost > OLD_COST
-      if (worse) alpha *= a.ls_decay;      // :268
-      searching = worse && n_pass < a.ls_cap;
+      ls.advance(delta, a.ls_decay);
+      searching = ls.searching(a.ls_cap);
     }
   }
-  int info_bits = 0;
-  if (worse) {                           // cap hit: the reference would still be looping; :274
-    alpha /= a.ls_decay;
-    info_bits |= 8;
-  }
-  if (!is_finite(cost)) info_bits |= 2;
-  if (live && lane == 0) {
-    a.costs[b] = cost;
-    if (a.old_costs != nullptr) a.old_costs[b] = old_cost;
-    a.alphas[b] = alpha;
-    a.n_ls[b] = n_pass;
-    if (a.info != nullptr && info_bits != 0) atomicOr(&a.info[b], info_bits);
-  }
+  if (ls.worse) ls.alpha = cap_alpha_sequential(ls.alpha, a.ls_decay);
+  // info_in, info_store: the dispatch hands neither to this kernel (mpc_search_route: both go to the pendulum's speculative
+  // searches alone, and DMPC_NO_SPEC_LS, which sends the pendulum here, switches BoxDDP's fused chain off with them)
+  if (live && lane == 0) search_store<false, false>(a, b, cost, old_cost, ls.alpha, ls.n_pass, search_flags(ls.worse, cost));
 }
 
 
@@ -909,9 +851,7 @@ __device__ __forceinline__ void mpc_forward_rec_pendulum_spec_body(const MpcFwdA
 #pragma unroll
       for (int i = NX - 1; i >= 0; --i) v = fmaf(sl.K[i], xh[i] - sl.xt[i], v);
       v += sl.uc;                                                                            // :209-219
-      v = fminf(fmaxf(v, sl.lb), sl.ub);                                                     // :221
-      v = (v - sl.lb <= bound_tol(sl.lb)) ? sl.lb : v;
-      v = (sl.ub - v <= bound_tol(sl.ub)) ? sl.ub : v;
+      v = box_clamp(v, sl.lb, sl.ub);
       const float tau[NS] = {xh[0], xh[1], xh[2], v};
       const float obj = quad(sl, tau);
       cost += obj;
@@ -1052,15 +992,12 @@ __device__ __forceinline__ void mpc_forward_rec_pendulum_spec_body(const MpcFwdA
       }
     }
   }
-  int info_bits = 0;
   int n_pass;
   if (p_sel < 0) {  // cap hit: the reference would still be looping; its last pass is the result        :274
     const int last = (a.ls_cap - 1) % NC;
-    alpha_sel = __shfl(alpha, base + last);
+    alpha_sel = cap_alpha_speculative(__shfl(alpha, base + last), a.ls_decay);
     cost_sel = __shfl(cost, base + last);
-    alpha_sel = (alpha_sel * a.ls_decay) / a.ls_decay;
     n_pass = a.ls_cap;
-    info_bits |= 8;
     float dummy = 0.f, c2 = 0.f;
     float al = 1.f;
     for (int i = 0; i < a.ls_cap - 1; ++i) al *= a.ls_decay;
@@ -1072,15 +1009,9 @@ __device__ __forceinline__ void mpc_forward_rec_pendulum_spec_body(const MpcFwdA
       pass(std::integral_constant<int, 2>{}, alpha_sel, c2, dummy);
     }
   }
-  if (!is_finite(cost_sel)) info_bits |= 2;
-  if (live && k == 0) {
-    if (a.info_in != nullptr) info_bits |= a.info_in[b];
-    a.costs[b] = cost_sel;
-    if (a.old_costs != nullptr) a.old_costs[b] = old_cost;
-    a.alphas[b] = alpha_sel;
-    a.n_ls[b] = n_pass;
-    if (a.info != nullptr && info_bits != 0) atomicOr(&a.info[b], info_bits);
-  }
+  // info_in merged: BoxDDP's fused chain (fused_select) hands this search the sweep's flags.  info_store ignored: only the
+  // one-launch iteration sets it, and that runs the wavefront-per-trajectory search below (iter_fused needs kSpec4).
+  if (live && k == 0) search_store<true, false>(a, b, cost_sel, old_cost, alpha_sel, n_pass, search_flags(p_sel < 0, cost_sel));
 }
 
 template <bool DMA>
@@ -1169,9 +1100,7 @@ __device__ __forceinline__ void mpc_forward_rec_pendulum_spec4_wave(const MpcFwd
       v = fmaf(Kk.y, xh[1] - xt[1], v);
       v = fmaf(Kk.x, xh[0] - xt[0], v);
       v += uc;                                                                               // :209-219
-      v = fminf(fmaxf(v, lb), ub);                                                           // :221
-      v = (v - lb <= bound_tol(lb)) ? lb : v;
-      v = (ub - v <= bound_tol(ub)) ? ub : v;
+      v = box_clamp(v, lb, ub);
       const float tau[NS] = {xh[0], xh[1], xh[2], v};
       const float d[NS] = {xh[0] - xt[0], xh[1] - xt[1], xh[2] - xt[2], v - uc};
       float qi = 0.f, qd = 0.f;   // (C tau)[sub], (C d)[sub]
@@ -1181,10 +1110,8 @@ __device__ __forceinline__ void mpc_forward_rec_pendulum_spec4_wave(const MpcFwd
       const float tau_s = pick4(tau[0], tau[1], tau[2], tau[3]);
       const float tau0_s = pick4(xt[0], xt[1], xt[2], uc);
       const float d_s = tau_s - tau0_s;
-      const float lin = fmaf(0.5f, qi, cs);
-      cost = fmaf(tau_s, lin, cost);                                                         // util.py:162-198
-      // obj(tau) - obj(tau0) without cancellation (see mpc_forward_rec_kernel): 1/2 d'(C tau) + 1/2 tau0'(C d) + c'd
-      delta += fmaf(d_s, lin, 0.5f * tau0_s * qd);
+      cost = fmaf(tau_s, fmaf(0.5f, qi, cs), cost);                                          // util.py:162-198 (summed by FMA)
+      delta += cost_row_diff(d_s, qi, cs, tau0_s, qd);
       if constexpr (WITH_OLD) old_cost = fmaf(tau0_s, fmaf(0.5f, qi - qd, cs), old_cost);    // :191, C tau0 = C tau - C d
       traj[t * Lay::SLOT + lane64] = tau_s;
       if (t < T - 1) {
@@ -1234,15 +1161,13 @@ __device__ __forceinline__ void mpc_forward_rec_pendulum_spec4_wave(const MpcFwd
       cost_sel = __shfl(cost, first);
     }
   }
-  int info_bits = 0;
+  const bool cap_hit = p_sel < 0;
   int n_pass;
-  if (p_sel < 0) {  // cap hit: the reference would still be looping; its last pass is the result        :274
+  if (cap_hit) {  // the reference would still be looping; its last pass is the result                    :274
     ks = (a.ls_cap - 1) % NC;   // still in LDS: a candidate of the last round
-    alpha_sel = __shfl(alpha, ks * 4);
+    alpha_sel = cap_alpha_speculative(__shfl(alpha, ks * 4), a.ls_decay);
     cost_sel = __shfl(cost, ks * 4);
-    alpha_sel = (alpha_sel * a.ls_decay) / a.ls_decay;
     n_pass = a.ls_cap;
-    info_bits |= 8;
   } else {
     n_pass = p_sel + 1;
   }
@@ -1282,18 +1207,9 @@ __device__ __forceinline__ void mpc_forward_rec_pendulum_spec4_wave(const MpcFwd
                               a.f_next != nullptr ? a.f_next + tb * 3 : nullptr);
     }
   }
-  if (!is_finite(cost_sel)) info_bits |= 2;
-  if (lane64 == 0) {
-    if (a.info_in != nullptr) info_bits |= a.info_in[b];
-    a.costs[b] = cost_sel;
-    if (a.old_costs != nullptr) a.old_costs[b] = old_cost;
-    a.alphas[b] = alpha_sel;
-    a.n_ls[b] = n_pass;
-    if (a.info != nullptr) {
-      if (a.info_store) a.info[b] = info_bits;
-      else if (info_bits != 0) atomicOr(&a.info[b], info_bits);
-    }
-  }
+  // info_in merged (fused_select hands it the sweep's flags) and info_store honoured: inside BoxDDP's one-launch iteration
+  // this search may run ahead of `done`, so its flags go to a staging word that the bookkeeping merges if the iteration counts
+  if (lane64 == 0) search_store<true, true>(a, b, cost_sel, old_cost, alpha_sel, n_pass, search_flags(cap_hit, cost_sel));
 }
 
 __global__ __launch_bounds__(256) void mpc_forward_rec_pendulum_spec4_kernel(const MpcFwdArgs a) {
@@ -1508,7 +1424,7 @@ __global__ __launch_bounds__(256) void active_mask_kernel(size_t n_rows, int nx,
   if (zero_a != nullptr && tid < (size_t)(ns * ns)) zero_a[tid] = 0.f;
   if (zero_b != nullptr && tid < (size_t)ns) zero_b[tid] = 0.f;
   for (size_t e = tid; e < n_rows * nu; e += stride)
-    active[e] = (fabsf(u[e] - lo[e]) <= bound_tol(lo[e])) || (fabsf(u[e] - hi[e]) <= bound_tol(hi[e]));
+    active[e] = on_bound(u[e], lo[e]) || on_bound(u[e], hi[e]);
   for (size_t e = tid; e < n_rows * ns; e += stride) {
     const size_t row = e / ns;
     const int j = (int)(e % ns);

@@ -254,7 +254,7 @@ __global__ __launch_bounds__(kTiledThreads) void pnqp_tiled_kernel(const PnqpTil
   }
   if (tid == 0) {
     a.n_iter_out[b] = o.it;
-    if (!o.converged && a.info != nullptr) atomicOr(&a.info[b], 4);     // DMPC_INFO_QP_ITERCAP
+    if (!o.converged && a.info != nullptr) atomicOr(&a.info[b], DMPC_INFO_QP_ITERCAP);
   }
 }
 
@@ -426,10 +426,11 @@ __global__ __launch_bounds__(kTiledThreads) void mpc_tiled_forward_kernel(const 
   float *xn = tau0 + ns;    // [nx]  next state in the making
   float *red = xn + nx;     // [4]
 
-  float alpha = 1.0f, cost = 0.f, old_cost = 0.f;
-  int n_pass = 0;
-  bool worse = true;
-  while (worse && n_pass < a.ls_cap) {                                                   // mpc_step.py:196
+  float cost = 0.f, old_cost = 0.f;
+  LineSearch ls;
+  while (ls.searching(a.ls_cap)) {
+    const float alpha = ls.alpha;
+    const bool first = ls.n_pass == 0;
     for (int i = tid; i < nx; i += NT) xh[i] = a.states[(size_t)b * nx + i];             // :198
     __syncthreads();
     cost = 0.f;
@@ -441,14 +442,11 @@ __global__ __launch_bounds__(kTiledThreads) void mpc_tiled_forward_kernel(const 
         float val = alpha * a.ks[tb * nu + m];
         for (int i = 0; i < nx; ++i) val = fmaf(Kr[i], xh[i] - a.states[tb * nx + i], val);
         val += a.controls[tb * nu + m];                                                  // :209-219
-        const float lb = a.lower[tb * nu + m], ub = a.upper[tb * nu + m];
-        val = fminf(fmaxf(val, lb), ub);                                                 // :221
-        val = (val - lb <= bound_tol(lb)) ? lb : val;
-        val = (ub - val <= bound_tol(ub)) ? ub : val;
+        val = box_clamp(val, a.lower[tb * nu + m], a.upper[tb * nu + m]);
         tau[nx + m] = val;
         tau0[nx + m] = a.controls[tb * nu + m];
         a.u[tb * nu + m] = val;
-        if (a.u_first != nullptr && n_pass == 0) a.u_first[tb * nu + m] = val;           // :260-263
+        if (a.u_first != nullptr && first) a.u_first[tb * nu + m] = val;                 // :260-263
       }
       for (int i = tid; i < nx; i += NT) {
         tau[i] = xh[i];
@@ -468,14 +466,14 @@ __global__ __launch_bounds__(kTiledThreads) void mpc_tiled_forward_kernel(const 
         }
         const float ci = a.c[tb * ns + i];
         const float di = tau[i] - tau0[i];
-        part += tau[i] * fmaf(0.5f, qi, ci);
-        part0 += tau0[i] * fmaf(0.5f, q0, ci);
-        partd += fmaf(di, fmaf(0.5f, qi, ci), 0.5f * tau0[i] * qd);
+        part += cost_row(tau[i], qi, ci);
+        part0 += cost_row(tau0[i], q0, ci);
+        partd += cost_row_diff(di, qi, ci, tau0[i], qd);
       }
       const float obj = tiled_block_sum(part, red);
       cost += obj;
       delta += tiled_block_sum(partd, red);
-      if (n_pass == 0) old_cost += tiled_block_sum(part0, red);                          // :191
+      if (first) old_cost += tiled_block_sum(part0, red);                                // :191
       if (a.objs != nullptr && tid == 0) a.objs[tb] = obj;
       if (t < T - 1)
         for (int i = tid; i < nx; i += NT) {                                             // :229-236
@@ -489,26 +487,12 @@ __global__ __launch_bounds__(kTiledThreads) void mpc_tiled_forward_kernel(const 
         for (int i = tid; i < nx; i += NT) xh[i] = xn[i];
       __syncthreads();
     }
-    ++n_pass;
-    worse = delta > 0.f;                 // :266  current_cost > OLD_COST
-    if (worse) alpha *= a.ls_decay;      // :268
+    ls.advance(delta, a.ls_decay);
   }
-  int info_bits = 0;
-  if (worse) {                           // cap hit: the reference would still be looping; :274
-    alpha /= a.ls_decay;
-    info_bits |= 8;
-  }
-  if (!is_finite(cost)) info_bits |= 2;
-  if (tid == 0) {
-    a.costs[b] = cost;
-    if (a.old_costs != nullptr) a.old_costs[b] = old_cost;
-    a.alphas[b] = alpha;
-    a.n_ls[b] = n_pass;
-    if (a.info != nullptr) {
-      const int merged = info_bits | (a.info_in != nullptr ? a.info_in[b] : 0);
-      if (merged != 0) atomicOr(&a.info[b], merged);
-    }
-  }
+  if (ls.worse) ls.alpha = cap_alpha_sequential(ls.alpha, a.ls_decay);
+  // info_in merged, by accident and unreachable: the dispatch hands an info_in to the pendulum's speculative searches alone
+  // (mpc_search_route), never to a LinDx shape.  info_store: never handed to this kernel.
+  if (tid == 0) search_store<true, false>(a, b, cost, old_cost, ls.alpha, ls.n_pass, search_flags(ls.worse, cost));
 }
 
 }  // namespace dmpc

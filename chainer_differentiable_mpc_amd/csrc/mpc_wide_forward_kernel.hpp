@@ -179,11 +179,11 @@ __global__ __launch_bounds__(256) void mpc_wide_forward_kernel(const MpcFwdArgs 
   };
 
   // OLD_COST and the test `current_cost > OLD_COST` on the per-timestep difference: see mpc_forward_rec_kernel
-  float old_cost = 0.f, alpha = 1.0f, cost = 0.f;
-  int n_pass = 0;
-  bool worse = true;
-  bool searching = a.ls_cap > 0;   // this trajectory's search goes on                      :196
+  float old_cost = 0.f, cost = 0.f;
+  LineSearch ls;
+  bool searching = ls.searching(a.ls_cap);   // this trajectory's search goes on
   for (int pass_idx = 0; __any(searching); ++pass_idx) {
+    const float alpha = ls.alpha;
     float xh = 0.f;                // new_x_t[lane] (lanes < NX)
     float cost_p = 0.f, old_p = 0.f, delta = 0.f;
     auto step = [&](int t) __attribute__((always_inline)) {
@@ -192,10 +192,8 @@ __global__ __launch_bounds__(256) void mpc_wide_forward_kernel(const MpcFwdArgs 
       float un[NU];
 #pragma unroll
       for (int m = 0; m < NU; ++m) {
-        float v = fmaf(alpha, ksv[m], group_sum<16>(is_x ? kvx[m] * dxv : 0.f)) + uc[m];   // :209-219
-        v = fminf(fmaxf(v, lb[m]), ub[m]);                                                   // :221
-        v = (v - lb[m] <= bound_tol(lb[m])) ? lb[m] : v;
-        un[m] = (ub[m] - v <= bound_tol(ub[m])) ? ub[m] : v;
+        const float v = fmaf(alpha, ksv[m], group_sum<16>(is_x ? kvx[m] * dxv : 0.f)) + uc[m];   // :209-219
+        un[m] = box_clamp(v, lb[m], ub[m]);
       }
       // [new_x_t ; new_u_t] and the iterate [x_t ; u_t], elements `lane` and 16 + lane
       float tau[2], tau0[2], dt[2];
@@ -218,12 +216,11 @@ __global__ __launch_bounds__(256) void mpc_wide_forward_kernel(const MpcFwdArgs 
       const float qi0 = row_dot(Crow0, tau, 0.f), qd0 = row_dot(Crow0, dt, 0.f);
       const float qi1 = row_dot(Crow1, tau, 0.f), qd1 = row_dot(Crow1, dt, 0.f);
       // per-lane partial sums over the timesteps; the lanes are added up once after the pass     :246-251, util.py:162-198
-      const float obj_l = tau[0] * fmaf(0.5f, qi0, c0) + (valid[1] ? tau[1] * fmaf(0.5f, qi1, c1) : 0.f);
+      const float obj_l = cost_row(tau[0], qi0, c0) + (valid[1] ? cost_row(tau[1], qi1, c1) : 0.f);
       cost_p += obj_l;
-      delta += fmaf(dt[0], fmaf(0.5f, qi0, c0), 0.5f * tau0[0] * qd0) +
-               (valid[1] ? fmaf(dt[1], fmaf(0.5f, qi1, c1), 0.5f * tau0[1] * qd1) : 0.f);
-      if (pass_idx == 0)   // cost of the iterate, from C tau = C tau' - C d                                 :191
-        old_p += tau0[0] * fmaf(0.5f, qi0 - qd0, c0) + (valid[1] ? tau0[1] * fmaf(0.5f, qi1 - qd1, c1) : 0.f);
+      delta += cost_row_diff(dt[0], qi0, c0, tau0[0], qd0) + (valid[1] ? cost_row_diff(dt[1], qi1, c1, tau0[1], qd1) : 0.f);
+      if (pass_idx == 0)                                                                                    // :191
+        old_p += cost_row_iterate(tau0[0], qi0, qd0, c0) + (valid[1] ? cost_row_iterate(tau0[1], qi1, qd1, c1) : 0.f);
       float obj = 0.f;
       if (a.objs != nullptr) obj = group_sum<16>(obj_l);
       if (searching) {  // outputs are overwritten by later passes; the last one is the accepted one
@@ -267,25 +264,13 @@ __global__ __launch_bounds__(256) void mpc_wide_forward_kernel(const MpcFwdArgs 
     if (pass_idx == 0) old_cost = group_sum<16>(old_p);
     if (searching) {
       cost = cost_p;
-      ++n_pass;
-      worse = delta > 0.f;                 // :266  current_cost > OLD_COST
-      if (worse) alpha *= a.ls_decay;      // :268
-      searching = worse && n_pass < a.ls_cap;
+      ls.advance(delta, a.ls_decay);
+      searching = ls.searching(a.ls_cap);
     }
   }
-  int info_bits = 0;
-  if (worse) {                           // cap hit: the reference would still be looping; :274
-    alpha /= a.ls_decay;
-    info_bits |= 8;
-  }
-  if (!is_finite(cost)) info_bits |= 2;
-  if (lane == 0) {
-    a.costs[b] = cost;
-    if (a.old_costs != nullptr) a.old_costs[b] = old_cost;
-    a.alphas[b] = alpha;
-    a.n_ls[b] = n_pass;
-    if (a.info != nullptr && info_bits != 0) atomicOr(&a.info[b], info_bits);
-  }
+  if (ls.worse) ls.alpha = cap_alpha_sequential(ls.alpha, a.ls_decay);
+  // info_in, info_store: the dispatch hands neither to this kernel (mpc_search_route refuses it a call with an info_in)
+  if (lane == 0) search_store<false, false>(a, b, cost, old_cost, ls.alpha, ls.n_pass, search_flags(ls.worse, cost));
 }
 
 }  // namespace dmpc

@@ -344,55 +344,26 @@ class MPCstep:
         Kd = _lib.f32c(_as_tensor(Ks), d)
         kd = _lib.f32c(_as_tensor(ks), d)
         assert len(Kd) == T, "Ks length error"
-        if isinstance(true_cost, QuadCost) and isinstance(true_dynamics, LinDx):
-            lib = _lib.load()
-            Ct, ct = _lib.f32c(_as_tensor(true_cost.C), d), _lib.f32c(_as_tensor(true_cost.c), d)
+        quad, p = isinstance(true_cost, QuadCost), _lib.ptr
+        # the dynamics a kernel's line search evaluates itself (mpc_step.py:237-240): its entry point, what that takes in
+        # front of the gains and what behind the cost
+        if quad and isinstance(true_dynamics, LinDx):
             Ft, ft = _lib.f32c(_as_tensor(true_dynamics.F), d), _lib.f32c(_as_tensor(true_dynamics.f), d)
-            f32 = dict(dtype=torch.float32, device=d)
-            x = torch.empty((T, B, nx), **f32)
-            u = torch.empty((T, B, nu), **f32)
-            u1 = torch.empty((T, B, nu), **f32)
-            costs = torch.empty((B,), **f32)
-            old = torch.empty((B,), **f32)
-            alphas = torch.empty((B,), **f32)
-            objs = torch.empty((T, B), **f32)
-            nls = torch.empty((B,), dtype=torch.int32, device=d)
-            info = torch.zeros(B, dtype=torch.int32, device=d)
-            with _lib.guard(d):
-                rc = lib.dmpc_mpc_forward_rec(T, B, nx, nu, _lib.ptr(Kd), _lib.ptr(kd), _lib.ptr(self._u),
-                                              _lib.ptr(self._xs), _lib.ptr(self._lo), _lib.ptr(self._hi),
-                                              _lib.ptr(Ct), _lib.ptr(ct), _lib.ptr(Ft), _lib.ptr(ft),
-                                              float(ls_decay), int(max_ls_iter), _lib.ptr(x), _lib.ptr(u),
-                                              _lib.ptr(costs), _lib.ptr(old), _lib.ptr(alphas), _lib.ptr(objs),
-                                              _lib.ptr(u1), _lib.ptr(nls), _lib.ptr(info), _lib.stream_ptr(d))
-            _lib.check(rc, "dmpc_mpc_forward_rec")
-            raise_info(info, "MPCstep.forward_rec")                                   # mpc_step.py:284-285
-        elif isinstance(true_cost, QuadCost) and _is_simple_pendulum(true_dynamics) and (nx, nu) == (3, 1):
-            # the pendulum of env_dx/pendulum.py evaluated inside the kernel's line search (mpc_step.py:237-240)
-            lib = _lib.load()
-            Ct, ct = _lib.f32c(_as_tensor(true_cost.C), d), _lib.f32c(_as_tensor(true_cost.c), d)
+            entry, head, dyn = "dmpc_mpc_forward_rec", (T, B, nx, nu), (p(Ft), p(ft))
+        elif quad and _is_simple_pendulum(true_dynamics) and (nx, nu) == (3, 1):     # env_dx/pendulum.py
             g_, m_, l_ = (float(v) for v in true_dynamics.params.detach().cpu().tolist())
-            f32 = dict(dtype=torch.float32, device=d)
-            x, u, u1 = torch.empty((T, B, nx), **f32), torch.empty((T, B, nu), **f32), torch.empty((T, B, nu), **f32)
-            costs, old, alphas = torch.empty((B,), **f32), torch.empty((B,), **f32), torch.empty((B,), **f32)
-            objs = torch.empty((T, B), **f32)
-            nls = torch.empty((B,), dtype=torch.int32, device=d)
-            info = torch.zeros(B, dtype=torch.int32, device=d)
-            with _lib.guard(d):
-                rc = lib.dmpc_mpc_forward_rec_pendulum(
-                    T, B, _lib.ptr(Kd), _lib.ptr(kd), _lib.ptr(self._u), _lib.ptr(self._xs), _lib.ptr(self._lo),
-                    _lib.ptr(self._hi), _lib.ptr(Ct), _lib.ptr(ct), g_, m_, l_, float(true_dynamics.dt),
-                    float(true_dynamics.max_torque), float(ls_decay), int(max_ls_iter), _lib.ptr(x), _lib.ptr(u),
-                    _lib.ptr(costs), _lib.ptr(old), _lib.ptr(alphas), _lib.ptr(objs), _lib.ptr(u1), _lib.ptr(nls),
-                    _lib.ptr(info), _lib.stream_ptr(d))
-            _lib.check(rc, "dmpc_mpc_forward_rec_pendulum")
-            raise_info(info, "MPCstep.forward_rec")
-        elif isinstance(true_cost, QuadCost) and _is_device_mlp(true_dynamics, nx, nu):
-            # a learned one-hidden-layer network evaluated inside the kernel's line search (mpc_step.py:237-240); its weights
-            # go in as device pointers
+            entry, head = "dmpc_mpc_forward_rec_pendulum", (T, B)
+            dyn = (g_, m_, l_, float(true_dynamics.dt), float(true_dynamics.max_torque))
+        elif quad and _is_device_mlp(true_dynamics, nx, nu):     # a learned one-hidden-layer network, weights as device pointers
+            W1, b1, W2, b2 = true_dynamics.device_weights(d)
+            entry, dyn = "dmpc_mpc_forward_rec_mlp", ()
+            head = (T, B, nx, nu, true_dynamics.n_hidden, true_dynamics.act_code, int(true_dynamics.residual),
+                    p(W1), p(b1), p(W2), p(b2))
+        else:
+            entry = None
+        if entry is not None:
             lib = _lib.load()
             Ct, ct = _lib.f32c(_as_tensor(true_cost.C), d), _lib.f32c(_as_tensor(true_cost.c), d)
-            W1, b1, W2, b2 = true_dynamics.device_weights(d)
             f32 = dict(dtype=torch.float32, device=d)
             x, u, u1 = torch.empty((T, B, nx), **f32), torch.empty((T, B, nu), **f32), torch.empty((T, B, nu), **f32)
             costs, old, alphas = torch.empty((B,), **f32), torch.empty((B,), **f32), torch.empty((B,), **f32)
@@ -400,14 +371,11 @@ class MPCstep:
             nls = torch.empty((B,), dtype=torch.int32, device=d)
             info = torch.zeros(B, dtype=torch.int32, device=d)
             with _lib.guard(d):
-                rc = lib.dmpc_mpc_forward_rec_mlp(
-                    T, B, nx, nu, true_dynamics.n_hidden, true_dynamics.act_code, int(true_dynamics.residual),
-                    _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), _lib.ptr(Kd), _lib.ptr(kd), _lib.ptr(self._u), _lib.ptr(self._xs),
-                    _lib.ptr(self._lo), _lib.ptr(self._hi), _lib.ptr(Ct), _lib.ptr(ct), float(ls_decay), int(max_ls_iter),
-                    _lib.ptr(x), _lib.ptr(u), _lib.ptr(costs), _lib.ptr(old), _lib.ptr(alphas), _lib.ptr(objs), _lib.ptr(u1),
-                    _lib.ptr(nls), _lib.ptr(info), _lib.stream_ptr(d))
-            _lib.check(rc, "dmpc_mpc_forward_rec_mlp")
-            raise_info(info, "MPCstep.forward_rec")
+                rc = getattr(lib, entry)(*head, p(Kd), p(kd), p(self._u), p(self._xs), p(self._lo), p(self._hi), p(Ct), p(ct),
+                                         *dyn, float(ls_decay), int(max_ls_iter), p(x), p(u), p(costs), p(old), p(alphas),
+                                         p(objs), p(u1), p(nls), p(info), _lib.stream_ptr(d))
+            _lib.check(rc, entry)
+            raise_info(info, "MPCstep.forward_rec")                                   # mpc_step.py:284-285
         else:
             x, u, u1, costs, alphas, objs, nls = self._forward_rec_callable(Kd, kd, true_cost, true_dynamics,
                                                                             ls_decay, max_ls_iter)
