@@ -10,8 +10,8 @@ Staleness is decided by CONTENT, not by mtimes: every object carries the SHA-256
 compiled from (its .hip, every header, the flags), and the library carries the hash of the whole
 source set twice - in `libdmpc_hip.so.srchash` next to it and inside the code (`dmpc_source_hash()`),
 so a library that does not belong to the sources in the tree is detected (`is_current()`), whatever
-the file times say.  Both generated headers (`lqr_asm_gen.hpp`, `dpp_blocks_gen.hpp`) are written here
-from their generators and are not kept in git.
+the file times say.  The five generated headers (`GENERATED` below) are written here from their
+generators and are not kept in git.
 """
 import argparse
 import concurrent.futures

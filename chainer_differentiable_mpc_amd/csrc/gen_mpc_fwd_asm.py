@@ -20,27 +20,40 @@ searches; a trajectory that is done neither stores nor commits (exec / select ma
 `cost > OLD_COST` is taken on the difference summed per timestep, obj(tau) - obj(tau^) = 1/2 d'(C tau) + 1/2 tau^'(C d) + c'd
 (see mpc_kernels.hpp), accumulated per lane and reduced over the row once per pass.
 
-    python chainer_differentiable_mpc_amd/csrc/gen_mpc_fwd_asm.py     # rewrites mpc_fwd_asm_gen.hpp
+    python chainer_differentiable_mpc_amd/csrc/gen_mpc_fwd_asm.py [--out PATH]    # rewrites mpc_fwd_asm_gen.hpp
 """
+import collections
 import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
-from gen_lqr_asm import Prog, Regs, VBASE   # noqa: E402  (emitter with the hazard tracker)
+from gen_asm_emit import LabelCounter, Prog, Regs, VBASE, v2   # noqa: E402  (emitter with the hazard tracker)
 
 OUT = os.path.join(HERE, "mpc_fwd_asm_gen.hpp")
 SHAPES = [(8, 2), (3, 1), (4, 2), (6, 2), (2, 2), (1, 1), (2, 1), (3, 2)]
 DB = 6        # ring depth == loop unroll (two alternating register sets)
-# timing experiments only (the results of such builds are wrong on purpose)
-X_NO_STORE = os.environ.get("GEN_FWD_NO_STORE") == "1"
-X_NO_DMA = os.environ.get("GEN_FWD_NO_DMA") == "1"
-X_NO_LDS = os.environ.get("GEN_FWD_NO_LDS") == "1"
-X_NO_COST = os.environ.get("GEN_FWD_NO_COST") == "1"
-X_NO_ADV = os.environ.get("GEN_FWD_NO_ADV") == "1"
-# later passes fetch only the chunks of the trajectories that still search (round 4; GEN_FWD_ROW_MASK=0: every pass fetches all)
-X_ROW_MASK = os.environ.get("GEN_FWD_ROW_MASK", "1") == "1"
-X_NT = os.environ.get("GEN_FWD_NT") == "1"      # nt cache policy on the input DMAs (measured, not a default: the search re-reads C and F)
+
+
+class Knobs(collections.namedtuple("Knobs", "no_store no_dma no_lds no_cost no_adv row_mask nt mfma_use")):
+    """the GEN_* variables of the line-search stream generator, one field each"""
+    __slots__ = ()
+
+    @classmethod
+    def from_env(cls, env):
+        return cls(
+            # timing experiments only (the results of such builds are wrong on purpose)
+            no_store=env.get("GEN_FWD_NO_STORE") == "1",
+            no_dma=env.get("GEN_FWD_NO_DMA") == "1",
+            no_lds=env.get("GEN_FWD_NO_LDS") == "1",
+            no_cost=env.get("GEN_FWD_NO_COST") == "1",
+            no_adv=env.get("GEN_FWD_NO_ADV") == "1",
+            # later passes fetch only the chunks of the trajectories that still search (round 4; GEN_FWD_ROW_MASK=0: every pass fetches all)
+            row_mask=env.get("GEN_FWD_ROW_MASK", "1") == "1",
+            nt=env.get("GEN_FWD_NT") == "1",      # nt cache policy on the input DMAs (measured, not a default: the search re-reads C and F)
+            # the LQR generator's MFMA knob reaches this stream through the emitter: wait states kept behind every label
+            mfma_use=int(env.get("GEN_MFMA_USE", "5")),
+        )
 
 
 class FwdLayout:
@@ -63,15 +76,12 @@ class FwdLayout:
         self.wide = nx % 2 == 0 and ns % 2 == 0  # rows are 8-byte aligned: ds_read_b64
 
 
-def v2(pair):
-    a = int(pair[0][1:])
-    return "v[%d:%d]" % (a, a + 1)
-
-
-def gen_fwd(nx, nu):
+def gen_fwd(nx, nu, K):
     L = FwdLayout(nx, nu)
     ns, KD = L.ns, L.kDma
-    P = Prog()
+    # This stream has no matrix instruction.  mfma_use is its post-label padding: the emitter keeps that many wait states
+    # between a label and the VALU instructions behind it, and the pinned stream has them.
+    P = Prog(mfma_use=K.mfma_use, mfma_dep=0)
     R = Regs(VBASE)
     ptr0 = ["%%[ptr0_%d]" % q for q in range(KD)]
     strd = ["%%[str%d]" % q for q in range(KD)]
@@ -96,12 +106,8 @@ def gen_fwd(nx, nu):
     S_DM = ["s[82:83]", "s[84:85]", "s[96:97]", "s[94:95]"]
     assert KD <= len(S_DM)
 
-    def mask64(lanes):
-        m16 = sum(1 << l for l in lanes)
-        return m16 | (m16 << 16)
-
-    uniq = [0]
-    in_body = [False]
+    labels = LabelCounter()
+    in_body = False     # inside a pass body: where the timing knobs drop things
 
     def issue_group(slot):
         if slot == 0:
@@ -111,24 +117,22 @@ def gen_fwd(nx, nu):
         P.raw("s_waitcnt lgkmcnt(0)")          # the wait state an LDS-DMA needs after the M0 write; the slot's reads are in
         for q in range(KD):
             off = (" offset:%d" % (q * 1024)) if q else ""
-            if not (X_NO_DMA and in_body[0]):
-                if X_ROW_MASK:   # only the chunks a searching trajectory needs (lane 0 always: the instruction is never empty,
+            if not (K.no_dma and in_body):
+                if K.row_mask:   # only the chunks a searching trajectory needs (lane 0 always: the instruction is never empty,
                     P.raw("s_mov_b64 exec, %s" % S_DM[q])      # the counted waits stay exact)
                     P.raw("s_nop 0")
-                P.raw("global_load_lds_dwordx4 %s, off%s%s" % (v2(PTR[q]), off, " nt" if X_NT else ""))
-        if X_ROW_MASK and not (X_NO_DMA and in_body[0]):
-            P.raw("s_mov_b64 exec, -1")
-            P.exec_written()
+                P.raw("global_load_lds_dwordx4 %s, off%s%s" % (v2(PTR[q]), off, " nt" if K.nt else ""))
+        if K.row_mask and not (K.no_dma and in_body):
+            P.exec_all()
 
     slow = []   # (label, return label): the one advance of a pass that must leave the F / f lanes where they are
 
     def advance():
         """move the DMA pointers one timestep on while there is one: S_TI counts the advances left; the LAST one (to
         t = T-1) uses the strides that keep the F / f lanes on slice T-2 (there is no F_{T-1}) - out of line"""
-        if X_NO_ADV and in_body[0]:
+        if K.no_adv and in_body:
             return
-        uniq[0] += 1
-        n_ = uniq[0]
+        n_ = labels.next()
         P.raw("s_cmp_lt_i32 %s, 2" % S_TI)
         P.raw("s_cbranch_scc1 Lslow%d_%%=" % n_)
         for q in range(KD):
@@ -148,7 +152,7 @@ def gen_fwd(nx, nu):
             P.raw("s_branch Ladv%d_%%=" % n_)
 
     def read_set(c, slot):
-        if X_NO_LDS and in_body[0]:
+        if K.no_lds and in_body:
             return
         S = sets[c]
         off = slot * L.SLOT_B
@@ -194,7 +198,7 @@ def gen_fwd(nx, nu):
         issue_group(j)                       # slot j went to registers one step ago: refill it, DB steps ahead
         advance()
         n_st = 1 + (1 if objs else 0) + (1 if uf else 0)
-        if not X_NO_DMA:
+        if not K.no_dma:
             P.raw("s_waitcnt vmcnt(%d)" % min(63, (DB - 1) * (KD + n_st)))
         read_set(o, (j + 1) % DB)
         # controls: u = clamp(u^ + alpha k + K (x - x^))                                           mpc_step.py:209-221
@@ -213,7 +217,7 @@ def gen_fwd(nx, nu):
         for m in range(nu):
             P.fmac_dpp(XN, TAU, ROW[nx + m], nx + m)                                                # u part
         # cost of the step and its difference to the iterate's                                      :246-251, util.py:162-198
-        if X_NO_COST:
+        if K.no_cost:
             ns_cost = 0
         else:
             ns_cost = ns
@@ -235,21 +239,18 @@ def gen_fwd(nx, nu):
         P.v("v_fmac_f32_e32 %s, %s, %s" % (OLDP, HAT, T2), writes=(OLDP,), reads=(HAT, T2, OLDP))
         # outputs of the trajectories that still search (the last pass that writes is the accepted one)
         if objs:
-            for rot in (8, 4, 2, 1):
-                P.valu("v_add_f32_dpp %s, %s, %s row_ror:%d row_mask:0xf bank_mask:0xf" % (OBJ, OBJ, OBJ, rot),
-                       writes=(OBJ,), reads=(OBJ,), dpp=OBJ)
+            row_sum(OBJ)
             P.raw("s_and_b64 exec, %s, %s" % (S_ROW0, S_SRCH))
-            if not X_NO_STORE:
+            if not K.no_store:
                 P.raw("global_store_dword %s, %s, off" % (v2(POBJ), OBJ))
         P.raw("s_mov_b64 exec, %s" % S_ST)
-        if not X_NO_STORE:
+        if not K.no_store:
             P.raw("global_store_dword %s, %s, off" % (v2(PST), TAU))
         if uf:
             P.raw("s_mov_b64 exec, %s" % S_UM)                                                     # :260-263 (first pass)
-            if not X_NO_STORE:
+            if not K.no_store:
                 P.raw("global_store_dword %s, %s, off" % (v2(PUF), TAU))
-        P.raw("s_mov_b64 exec, -1")
-        P.exec_written()
+        P.exec_all()
         if objs:
             P.v("v_lshl_add_u64 %s, %s, 0, %%[dobj]" % (v2(POBJ), v2(POBJ)))
         P.v("v_lshl_add_u64 %s, %s, 0, %%[dst]" % (v2(PST), v2(PST)))
@@ -258,15 +259,12 @@ def gen_fwd(nx, nu):
 
     def row_sum(reg):
         for rot in (8, 4, 2, 1):
-            P.valu("v_add_f32_dpp %s, %s, %s row_ror:%d row_mask:0xf bank_mask:0xf" % (reg, reg, reg, rot),
+            P.v("v_add_f32_dpp %s, %s, %s row_ror:%d row_mask:0xf bank_mask:0xf" % (reg, reg, reg, rot),
                    writes=(reg,), reads=(reg,), dpp=reg)
 
     # =============================================================== set-up
-    for name, val in ((S_XM, mask64(range(nx))), (S_UM, mask64(range(nx, ns))), (S_SM, mask64(range(ns))),
-                      (S_ROW0, mask64([0]))):
-        lo = int(name[2:name.index(":")])
-        P.raw("s_mov_b32 s%d, 0x%x" % (lo, val & 0xffffffff))
-        P.raw("s_mov_b32 s%d, 0x%x" % (lo + 1, val & 0xffffffff))
+    for pair, lanes in ((S_XM, range(nx)), (S_UM, range(nx, ns)), (S_SM, range(ns)), (S_ROW0, [0])):
+        P.load_mask(pair, lanes)
     # (hipcc gives an inline-asm block only a handful of "s" operands: the rest come as VGPRs, same in every lane)
     P.raw("v_readfirstlane_b32 %s, %%[cap]" % S_CAP)
     P.raw("v_readfirstlane_b32 %s, %%[want_objs]" % S_WOBJ)
@@ -280,7 +278,7 @@ def gen_fwd(nx, nu):
     P.raw("s_mov_b64 %s, -1" % S_SRCH)
     # =============================================================== one pass of the line search
     P.label("Lpass_%=")
-    if X_ROW_MASK:
+    if K.row_mask:
         # A later pass is run for the trajectories that still search; the others' chunks of the slot are not fetched again
         # (their lanes compute on whatever the ring holds - finite leftovers - and commit nothing): rb = the searching
         # rows as four bits, S_DM[q] = the lanes whose chunk of DMA q holds data of a searching row (a chunk can straddle rows)
@@ -337,10 +335,9 @@ def gen_fwd(nx, nu):
         P.raw("s_mov_b64 exec, %s" % S_ST)
         for _ in range((DB - 1) * n_st):
             P.raw("global_store_dword %s, %s, off" % (v2(PST), XA))
-        P.raw("s_mov_b64 exec, -1")
-        P.exec_written()
+        P.exec_all()
         P.label("Lloop%d_%%=" % idx, reset=False)
-        in_body[0] = True
+        in_body = True
         for j in range(DB):
             c = j % 2
             X, XN = (XA, XB) if c == 0 else (XB, XA)
@@ -352,7 +349,7 @@ def gen_fwd(nx, nu):
                 P.raw("s_cbranch_scc0 Lpassend_%=")
             else:
                 P.raw("s_cbranch_scc1 Lloop%d_%%=" % idx)
-        in_body[0] = False
+        in_body = False
         if idx < 3:
             P.raw("s_branch Lpassend_%=")
     P.label("Lpassend_%=")
@@ -454,18 +451,24 @@ struct MpcFwdAsm {
 """
 
 
-def main():
+def header_text(knobs):
+    """the whole of mpc_fwd_asm_gen.hpp under `knobs`"""
     out = [HEADER]
     for nx, nu in SHAPES:
         try:
-            out.append(gen_fwd(nx, nu))
+            out.append(gen_fwd(nx, nu, knobs))
         except AssertionError as e:     # a shape whose slot has no room for the zero reads: no stream
             print("skip (%d,%d): %s" % (nx, nu, e))
     out.append("}  // namespace dmpc\n")
-    with open(OUT, "w") as fh:
-        fh.write("".join(out))
-    print("wrote", OUT)
+    return "".join(out)
+
+
+def main(argv):
+    out = argv[2] if len(argv) > 2 and argv[1] == "--out" else OUT
+    with open(out, "w") as fh:
+        fh.write(header_text(Knobs.from_env(os.environ)))
+    print("wrote", out)
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv)
