@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from .approximate import approximate_cost, linearize_dynamics
 from .lqr_recursion import _as_tensor, _device_of, _workspace
+from .mlp_dx import MlpDx
 from .mpc_step import MPCstep, _MPCstepTiledDxFn, _MPCstepTiledFn, _is_simple_pendulum
 from .util import LinDx, QuadCost, TiledLinDx, TiledQuadCost, get_cost, get_traj
 
@@ -57,8 +58,8 @@ class BoxDDP(torch.nn.Module):
         self.exit_unconverged = exit_unconverged
         self.update_dynamics = update_dynamics
         self.quiet = quiet          # suppress the reference's "Converged" / "Not improved lim" prints
-        # QuadCost with a LinDx or the built-in pendulum: the whole loop is one chain of launches with the
-        # stop tests on the device (`dmpc_box_ddp`); False keeps the host loop over MPCstep objects
+        # QuadCost with a LinDx, the built-in pendulum or an `MlpDx(device_loop=True)`: the whole loop is one chain of launches
+        # with the stop tests on the device (`dmpc_box_ddp`); False keeps the host loop over MPCstep objects
         self.device_loop = device_loop
         # PNQP termination inside every MPC step: per trajectory (default; shard-invariant) or the reference's
         # batch-global tests (pnqp.py:139-144,172,187; the batch must fit one cooperative launch).  The outer
@@ -179,6 +180,13 @@ class BoxDDP(torch.nn.Module):
             return x.to(x_init.dtype)
         return get_traj(T, u, x_init, dyn)
 
+    @staticmethod
+    def _mlp_fused_ok(dynamics, x_init, u):
+        """GPU tensors and a size the kernels serve.  Asked as the host loop asks it, with no gradient in sight: the chain
+        replaces the loop only, and a gradient comes from forward()'s no-op node around `dynamics.linearize` afterwards."""
+        with torch.no_grad():
+            return dynamics.fused_ok(x_init, u)
+
     def _device_loop(self, x_init, cost, dynamics, u, lo, hi):
         """box_ddp.py:123-230 behind one C call; returns (best, last full_du_norm) or None when the problem is not
         of the supported kind (then the host loop runs)."""
@@ -191,6 +199,12 @@ class BoxDDP(torch.nn.Module):
             params = (ctypes.c_float * 6)(g_, m_, l_, float(dynamics.dt), float(dynamics.max_torque),
                                           1.0 if dynamics.clamp_grad_closed else 0.0)
             kind, Fd, fd = 1, None, None
+        elif isinstance(dynamics, MlpDx) and dynamics.device_loop and not self.batch_coupled and \
+                (nx, nu) == (dynamics.n_state, dynamics.n_ctrl) and self._mlp_fused_ok(dynamics, x_init, u):
+            # the network inside the chain (dyn_kind 2): F is the model's packed weights, refilled below on EVERY call - also
+            # the one that replays a recording, which reads the same buffer
+            params = (ctypes.c_float * 4)(*dynamics.host_params())
+            kind, Fd, fd = 2, None, None
         else:
             return None
         lib = _lib.load()
@@ -205,7 +219,9 @@ class BoxDDP(torch.nn.Module):
         f = None if fd is None else _lib.f32c(_as_tensor(fd).detach(), d)
         if list(C.shape) != [T, B, ns, ns] or list(c.shape) != [T, B, ns]:
             return None
-        if F is not None and (F.shape[0] not in (T - 1, T) or list(F.shape[1:]) != [B, nx, ns]):
+        if kind == 2:
+            F = dynamics.packed_weights(d)       # (one launch; the same address on every call)
+        elif F is not None and (F.shape[0] not in (T - 1, T) or list(F.shape[1:]) != [B, nx, ns]):
             return None
         if f is not None and list(f.shape) != [T - 1, B, nx]:
             return None
@@ -319,7 +335,8 @@ class BoxDDP(torch.nn.Module):
                 self._resolve()                   # the one synchronisation of the loop
         dev, dt = x_init.device, x_init.dtype
         self.__dict__["_fast"] = None
-        if entry is not None and entry[0] is not None and dt == torch.float32 and dev == d and x0 is not None and \
+        # (never for the network: _replay does not come through here, and a replay must follow a refill of the packed weights)
+        if kind != 2 and entry is not None and entry[0] is not None and dt == torch.float32 and dev == d and x0 is not None and \
                 x0.data_ptr() == x_init.data_ptr() and C.data_ptr() == cost.C.data_ptr() and c.data_ptr() == cost.c.data_ptr():
             # what forward() checks before it replays this recording without going through any of the above
             self.__dict__["_fast"] = (entry, x_init, cost, cost.C, cost.c, dynamics, x0.data_ptr(), C.data_ptr(), c.data_ptr(),

@@ -31,6 +31,21 @@ static void mlp_with_act(int act, Fn &&fn) {
   }
 }
 
+// the two launchers of mlp_dx_launch.hpp: the entry points below and dmpc_box_ddp's chain (mpc_api.hip) go through them
+void launch_mlp_rollout(const MlpRolloutArgs &a, int act, hipStream_t stream) {
+  mlp_with_act(act, [&](auto A) {
+    DMPC_LAUNCH_GGL(mlp_rollout_linearize_kernel<decltype(A)::value>, dim3((a.B + kMlpWaves - 1) / kMlpWaves),
+                    dim3(64 * kMlpWaves), mlp_lds_bytes(a.m.nx, a.m.nu, a.m.n_hidden), stream, a);
+  });
+}
+
+void launch_mlp_search(const MpcFwdArgs &a, const MlpModel &m, int act, hipStream_t stream) {
+  mlp_with_act(act, [&](auto A) {
+    DMPC_LAUNCH_GGL(mpc_forward_rec_mlp_kernel<decltype(A)::value>, dim3((a.B + kMlpWaves - 1) / kMlpWaves),
+                    dim3(64 * kMlpWaves), mlp_lds_bytes(m.nx, m.nu, m.n_hidden), stream, a, m);
+  });
+}
+
 }  // namespace dmpc
 
 using namespace dmpc;
@@ -49,10 +64,7 @@ int dmpc_mlp_rollout_linearize(int T, int B, int nx, int nu, int n_hidden, int a
   if (rc != 0) return rc;
   if ((size_t)T * B * nx * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;
   MlpRolloutArgs ra{T, B, MlpModel{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2}, x_init, u, x_out, F_out, f_out};
-  mlp_with_act(act, [&](auto A) {
-    DMPC_LAUNCH_GGL(mlp_rollout_linearize_kernel<decltype(A)::value>, dim3((B + kMlpWaves - 1) / kMlpWaves),
-                    dim3(64 * kMlpWaves), mlp_lds_bytes(nx, nu, n_hidden), static_cast<hipStream_t>(stream_), ra);
-  });
+  launch_mlp_rollout(ra, act, static_cast<hipStream_t>(stream_));   // (no `done` flag, nothing to clear)
   return (int)hipGetLastError();
 }
 
@@ -72,10 +84,7 @@ int dmpc_mpc_forward_rec_mlp(int T, int B, int nx, int nu, int n_hidden, int act
   MpcFwdArgs fa{T, B, Ks, ks, controls, states, u_lower, u_upper, C_true, c_true, nullptr, nullptr, ls_decay,
                 max_ls_iter, /*ls_cap=*/64, x_out, u_out, u_first, costs, old_costs, alphas, objs, n_ls_iter, info};
   const MlpModel m{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2};
-  mlp_with_act(act, [&](auto A) {
-    DMPC_LAUNCH_GGL(mpc_forward_rec_mlp_kernel<decltype(A)::value>, dim3((B + kMlpWaves - 1) / kMlpWaves),
-                    dim3(64 * kMlpWaves), mlp_lds_bytes(nx, nu, n_hidden), static_cast<hipStream_t>(stream_), fa, m);
-  });
+  launch_mlp_search(fa, m, act, static_cast<hipStream_t>(stream_));  // (fa.done, fa.F_next: nullptr)
   return (int)hipGetLastError();
 }
 

@@ -41,6 +41,7 @@
 #pragma clang attribute push(__attribute__((internal_linkage)), apply_to = function)
 #include "mpc_generic.hpp"
 #pragma clang attribute pop
+#include "mlp_dx_launch.hpp"      // MlpModel, MlpRolloutArgs
 
 namespace dmpc {
 
@@ -48,11 +49,6 @@ constexpr int kMlpMaxNx = 16, kMlpMaxNu = 8, kMlpMaxHidden = 256;
 constexpr int kMlpWaves = 4;                                 // trajectories (wavefronts) per workgroup
 constexpr int kMlpUnits = kMlpMaxHidden / 64;                // hidden units per lane, at most
 constexpr int kMlpWaveFloats = kMlpMaxHidden + kMlpMaxNx * (kMlpMaxNx + kMlpMaxNu) + 32;
-
-struct MlpModel {
-  int nx, nu, n_hidden, residual;
-  const float *W1, *b1, *W2, *b2;   // [H,ns], [H], [nx,H], [nx]  (device pointers: an optimiser step is seen by the next launch)
-};
 
 struct MlpLds {
   int nsp, hp;                      // row strides of W1s and W2s
@@ -199,16 +195,13 @@ __device__ __forceinline__ void mlp_jacobian_store(const MlpModel &m, const MlpL
   if (fq != nullptr && lane < nx) fq[lane] = f;
 }
 
-struct MlpRolloutArgs {
-  int T, B;
-  MlpModel m;
-  const float *x_init, *u;   // [B,nx], [T,B,nu]
-  float *x, *F, *f;          // [T,B,nx]; [T-1,B,nx,ns] or nullptr; [T-1,B,nx] or nullptr
-};
-
+// (MlpRolloutArgs: mlp_dx_launch.hpp.)  In a box-DDP chain: a.clear runs first - thread g of the grid zeroes word g of each
+// range, and the grid has at least max(B, 256) threads - and a set `done` flag ends the launch before its barrier.
 template <int ACT>
 __global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(const MlpRolloutArgs a) {
   extern __shared__ float lds[];
+  a.clear.run(blockIdx.x * blockDim.x + threadIdx.x);
+  if (a.done != nullptr && *a.done != 0) return;   // grid-uniform: the iLQR loop has stopped
   const MlpLds L = mlp_stage(a.m, lds);
   const int lane = threadIdx.x % 64;
   const int b = blockIdx.x * kMlpWaves + threadIdx.x / 64;
@@ -233,9 +226,13 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(c
 // through it mpc_forward_rec_kernel's): the cost difference per timestep without cancellation, box_clamp's snap, the
 // pass cap.  a.F / a.f are not read.  The loop is wave-uniform by construction - a wavefront is one trajectory - so a
 // trajectory that has finished runs, stores and commits nothing more.
+// a.F_next (BoxDDP's chain): the accepted trajectory IS the next iteration's nominal one, so after the search the wavefront
+// walks it once more and stores its Jacobians, F_next [T-1,B,nx,ns] - through mlp_next and mlp_jacobian_store on the values
+// mlp_rollout_linearize_kernel would start from, hence bit for bit what that kernel would store.  a.f_next, a.c_next: not written.
 template <int ACT>
 __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(const MpcFwdArgs a, const MlpModel m) {
   extern __shared__ float lds[];
+  if (a.done != nullptr && *a.done != 0) return;   // grid-uniform, before the barrier: the iLQR loop has stopped
   const MlpLds L = mlp_stage(m, lds);
   const int lane = threadIdx.x % 64;
   const int b = blockIdx.x * kMlpWaves + threadIdx.x / 64;
@@ -307,6 +304,20 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(con
   if (ls.worse) ls.alpha = cap_alpha_sequential(ls.alpha, a.ls_decay);
   // info_in, info_store: dmpc_mpc_forward_rec_mlp has neither (its MpcFwdArgs leaves both zero)
   if (lane == 0) search_store<false, false>(a, b, cost, old_cost, ls.alpha, ls.n_pass, search_flags(ls.worse, cost));
+  if (a.F_next != nullptr) {
+    // the last pass is the accepted one: its controls are in a.u, each re-read by the lane that stored it; the states are
+    // re-evaluated from states[0] by the function that formed them
+    float xc = is_x ? a.states[(size_t)b * nx + lane] : 0.f;
+    for (int t = 0; t < T - 1; ++t) {
+      const size_t tb = (size_t)t * B + b;
+      const float v = a.u[tb * nu + mu];
+      const float tau = is_x ? xc : (is_u ? v : 0.f);
+      float act[kMlpUnits], dact[kMlpUnits];
+      const float xn = mlp_next<ACT>(m, L, lane, tau, act, dact);
+      mlp_jacobian_store(m, L, lane, tau, xn, dact, a.F_next + tb * nx * ns, nullptr);
+      xc = xn;
+    }
+  }
 }
 
 // The gradient of L(f) with respect to W1, b1, W2, b2 for f_t = next(x_t, u_t) - F_t [x_t;u_t] along the rolled states,

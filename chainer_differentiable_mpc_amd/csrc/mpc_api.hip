@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 
 #include "../../include/dmpc.h"
 #include "api_util.hpp"
@@ -21,6 +22,7 @@
 #include "mpc_tiled.hpp"
 #include "mpc_coupled.hpp"
 #include "mpc_kernels.hpp"
+#include "mlp_dx_launch.hpp"
 
 namespace dmpc {
 
@@ -990,7 +992,22 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
     return DMPC_E_BADARG;
   if (dyn_kind == 0 && !F) return DMPC_E_BADARG;
   if (dyn_kind == 1 && (!dyn_params || nx != 3 || nu != 1)) return DMPC_E_BADARG;
-  if (dyn_kind != 0 && dyn_kind != 1) return DMPC_E_UNSUPPORTED;
+  if (dyn_kind < 0 || dyn_kind > 2) return DMPC_E_UNSUPPORTED;
+  // MlpDx: F is the packed weights, dyn_params = {n_hidden, act, residual, search_linearizes} on the host
+  int mlp_hidden = 0, mlp_act = 0, mlp_residual = 0, mlp_search_lin = 0;
+  if (dyn_kind == 2) {
+    if (!F || f != nullptr || !dyn_params) return DMPC_E_BADARG;
+    const float h = dyn_params[0], ac = dyn_params[1], res = dyn_params[2], sl = dyn_params[3];
+    if (!(h >= 0.f) || h != floorf(h) || !(ac >= 0.f) || ac != floorf(ac)) return DMPC_E_BADARG;   // (a NaN fails `>=`)
+    if ((res != 0.f && res != 1.f) || (sl != 0.f && sl != 1.f)) return DMPC_E_BADARG;
+    mlp_hidden = h > 1e6f ? 1000000 : (int)h;
+    mlp_act = ac > 1e6f ? 1000000 : (int)ac;
+    mlp_residual = res != 0.f;
+    mlp_search_lin = sl != 0.f;
+    if (!dmpc_mlp_dx_supported(nx, nu, mlp_hidden, mlp_act) || batch_coupled) return DMPC_E_UNSUPPORTED;
+    // (the limits of dmpc_mlp_rollout_linearize and dmpc_mpc_forward_rec_mlp)
+    if ((size_t)T * B * (nx + nu) * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;
+  }
   // (round 5: shapes that run on the tiled kernels - more than 8 controls / 64 columns - too: their matrices live in w.tiled)
   if ((size_t)T * B * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;  // 32-bit indices in the bookkeeping
   if (!aligned16(C) || !aligned16(c) || !aligned16(F) || !aligned16(f) || !aligned16(ws)) return DMPC_E_BADARG;
@@ -1020,6 +1037,11 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   // linearisation and re-centred cost while it writes the trajectory - the rollout + linearisation kernel runs for
   // the first iteration only, the nominal states ping-pong between the two state buffers.
   const bool fuse_lin = dyn_kind == 1 && !knob_on<Knob::DMPC_NO_SPEC_LS>();
+  // MlpDx: the same, on request (search_linearizes) - the search's epilogue stores the accepted trajectory's Jacobians
+  // through the rollout kernel's own two functions, so both settings return the same bits.  The re-centring stays the sweep's.
+  const bool mlp = dyn_kind == 2, mlp_lin = mlp && mlp_search_lin != 0;
+  const MlpModel mlp_model = mlp ? mlp_model_packed(nx, nu, mlp_hidden, mlp_residual, F) : MlpModel{};
+  const bool ping_pong = fuse_lin || mlp_lin;   // the nominal states alternate between the two state buffers
   float *x_buf[2] = {xs, x_new};
   const bool copy_here = B <= kDdpCopyHereMaxB && rows * (size_t)(nx + nu) <= kDdpCopyHereMaxElems;
   // MPCstep.forward with need_expand: f_hat = None                                        mpc_step.py:305-328
@@ -1036,7 +1058,7 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
                       dyn_kind == 0 ? f : nullptr, ls_decay, max_ls_iter, /*ls_cap=*/64, xn_it, u_new, u1_it, costs_it,
                       /*old_costs: nobody reads them here*/ nullptr,
                       alphas, nullptr, ip(w.nls), info, dyn_kind, pg, pm, pl, pdt, pmax, pclosed, done,
-                      fuse_lin ? fp(w.F) : nullptr, fuse_lin ? fp(w.f) : nullptr, fuse_lin ? c_back : nullptr, 0,
+                      fuse_lin || mlp_lin ? fp(w.F) : nullptr, fuse_lin ? fp(w.f) : nullptr, fuse_lin ? c_back : nullptr, 0,
                       fused_select && info != nullptr ? ip(w.info_back) : nullptr};
   };
   // Every route the chain takes, asked before its first launch: [0] the first iteration, which reads the caller's controls in
@@ -1047,8 +1069,9 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   sweep[0] = mpc_sweep_route(sweep_call(nx, nu, back_args(u_init, xs), false, true));
   fused_select = fuse_lin && copy_here && (sweep[0].kind == MpcKernel::kStream || sweep[0].kind == MpcKernel::kRing);
   sweep[1] = mpc_sweep_route(sweep_call(nx, nu, back_args(u_buf[1], x_new), fused_select, true));
-  search[0] = mpc_search_route(search_call(nx, nu, fwd_args(u_init, xs, x_new, u_buf[1], u1, costs)));
-  search[1] = mpc_search_route(search_call(nx, nu, fwd_args(u_buf[1], x_new, xs, u_buf[0], u1, costs)));
+  // (MlpDx: the network's search is no row of mpc_search_route - it is this chain's branch on dyn_kind, checked above)
+  search[0] = mlp ? MpcSearchRoute{0} : mpc_search_route(search_call(nx, nu, fwd_args(u_init, xs, x_new, u_buf[1], u1, costs)));
+  search[1] = mlp ? MpcSearchRoute{0} : mpc_search_route(search_call(nx, nu, fwd_args(u_buf[1], x_new, xs, u_buf[0], u1, costs)));
   for (const int code : {sweep[0].code, search[0].code, sweep[1].code, search[1].code})
     if (code != 0) return code;
   DdpSelectArgs sa{};
@@ -1068,8 +1091,8 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
     const float *u_cur = it == 0 ? u_init : (iter_fused ? u_buf3[it % 3] : u_buf[it & 1]);   // the first iteration reads the caller's controls in place
     float *u_new = iter_fused ? u_buf3[(it + 1) % 3] : u_buf[(it & 1) ^ 1];
     float *u1_it = iter_fused ? u1_2[it & 1] : u1, *costs_it = iter_fused ? costs_2[it & 1] : costs;
-    float *xs_it = fuse_lin ? x_buf[it & 1] : xs;
-    float *xn_it = fuse_lin ? x_buf[(it & 1) ^ 1] : x_new;
+    float *xs_it = ping_pong ? x_buf[it & 1] : xs;
+    float *xn_it = ping_pong ? x_buf[(it & 1) ^ 1] : x_new;
     const int k = it == 0 ? 0 : 1;
     // nominal trajectory and the Taylor models around it                                    box_ddp.py:123-171
     PendulumArgs pa_first{};     // one-launch iterations: the first iteration's launch rolls out and linearises itself (pa_first.T > 0)
@@ -1079,6 +1102,13 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
                         c_back, it == 0 ? clear : ChainClear{}};
         if (iter_fused) pa_first = pa;
         else launch_pendulum_rollout(pa, stream);
+      }
+    } else if (mlp) {
+      // f is not formed: with need_expand the step drops f_hat                               mpc_step.py:305-328
+      if (it == 0 || !mlp_lin) {
+        MlpRolloutArgs ra{T, B, mlp_model, x_init, u_cur, xs_it, fp(w.F), nullptr, it == 0 ? nullptr : done,
+                          it == 0 ? clear : ChainClear{}};
+        launch_mlp_rollout(ra, mlp_act, stream);
       }
     } else {
       DMPC_LAUNCH_GGL(lin_rollout_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, T, B, nx, nu, x_init, u_cur, F,
@@ -1107,7 +1137,12 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
     } else {
       rc = run_sweep(sweep[k], nx, nu, ba, stream, fused_select && it > 0 ? &sa : nullptr, sel_sync);
       if (rc != 0) return rc;
-      rc = search[k].launch({fa, nx, nu}, stream);
+      if (mlp) {
+        launch_mlp_search(fa, mlp_model, mlp_act, stream);
+        rc = (int)hipGetLastError();
+      } else {
+        rc = search[k].launch({fa, nx, nu}, stream);
+      }
       if (rc != 0) return rc;
     }
     // best-so-far update and stop tests of this iteration                                   box_ddp.py:200-230

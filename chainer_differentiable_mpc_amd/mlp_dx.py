@@ -10,6 +10,10 @@ evaluates the network inside its kernel (`dmpc_mpc_forward_rec_mlp`); the hooks 
 `fused_ok`, `rollout_linearize`).  The weights go to the library as device pointers on every call: nothing is read back and
 nothing is cached, so an optimiser step in place is seen by the next call.
 
+`BoxDDP` drives those kernels from its host loop.  With `device_loop=True` it runs the whole iLQR loop as one chain of launches
+instead (`dmpc_box_ddp`, dyn_kind 2: the weights as one packed buffer, `packed_weights`), where the chain serves the problem -
+GPU tensors, a supported size, a dense `QuadCost`, no `batch_coupled`; anything else keeps the host loop.
+
 Learning the weights follows mpc/approximate.py:77-119: the Jacobians F_t are constants of the graph, f_t = next - F_t [x;u]
 stays on it through `next` and the re-rolled states, and `MPCstep.backward`'s df reaches W1, b1, W2, b2.  By default that
 graph is a live torch rollout; with `device_grad=True` it is one autograd node around the rollout's launch whose backward
@@ -42,12 +46,20 @@ _ACT_OF_MODULE = {torch.nn.Tanh: "tanh", torch.nn.ReLU: "relu", torch.nn.SiLU: "
 
 
 class MlpDx(torch.nn.Module):
-    def __init__(self, n_state, n_ctrl, n_hidden, residual=True, seed=None, device_grad=False, activation="tanh"):
+    # `search_linearizes` of dmpc_box_ddp's dyn_kind 2 as `BoxDDP` passes it: both settings return the same bits, and 0 measured
+    # no slower at either size of DESIGN.md 3.10 (the chain is bound by its kernels, not by its launches)
+    SEARCH_LINEARIZES = False
+
+    def __init__(self, n_state, n_ctrl, n_hidden, residual=True, seed=None, device_grad=False, activation="tanh",
+                 device_loop=False):
         super().__init__()
         if activation not in ACTIVATIONS:
             raise ValueError("MlpDx: unknown activation %r (one of %s)" % (activation, ", ".join(ACTIVATIONS)))
         self.activation = activation
         self.device_grad = bool(device_grad)
+        # BoxDDP runs its iLQR loop as one chain of launches (`dmpc_box_ddp`, dyn_kind 2) where the chain serves the problem
+        self.device_loop = bool(device_loop)
+        self._packed = {}           # device -> the flat weight buffer of `packed_weights` (no parameter, no buffer, not pickled)
         self.n_state, self.n_ctrl, self.n_hidden = int(n_state), int(n_ctrl), int(n_hidden)
         self.residual = bool(residual)
         ns = self.n_state + self.n_ctrl
@@ -59,7 +71,7 @@ class MlpDx(torch.nn.Module):
         self._size_ok = None
 
     @classmethod
-    def from_sequential(cls, net, n_state, n_ctrl, residual=True, device_grad=False):
+    def from_sequential(cls, net, n_state, n_ctrl, residual=True, device_grad=False, device_loop=False):
         """the model of a trained `torch.nn.Sequential(Linear(n_state + n_ctrl, H), act, Linear(H, n_state))` whose input is
         [x;u], act one of Tanh, ReLU, SiLU, Softplus (beta = 1, threshold = 20).  The four tensors are copied; anything else is
         a ValueError that names what was found."""
@@ -80,15 +92,22 @@ class MlpDx(torch.nn.Module):
         if l1.in_features != n_state + n_ctrl or l2.out_features != n_state or l2.in_features != l1.out_features:
             raise ValueError("MlpDx.from_sequential: want Linear(%d, H) and Linear(H, %d), found %s"
                              % (n_state + n_ctrl, n_state, found))
-        m = cls(n_state, n_ctrl, l1.out_features, residual=residual, device_grad=device_grad, activation=name)
+        m = cls(n_state, n_ctrl, l1.out_features, residual=residual, device_grad=device_grad, activation=name,
+                device_loop=device_loop)
         with torch.no_grad():
             for p, q in zip(m._weights(), (l1.weight, l1.bias, l2.weight, l2.bias)):
                 p.copy_(q.detach())
         return m.to(device=l1.weight.device, dtype=l1.weight.dtype)
 
     def extra_repr(self):
-        return "n_state=%d, n_ctrl=%d, n_hidden=%d, residual=%s, activation=%s, device_grad=%s" % (
-            self.n_state, self.n_ctrl, self.n_hidden, self.residual, self.activation, self.device_grad)
+        return "n_state=%d, n_ctrl=%d, n_hidden=%d, residual=%s, activation=%s, device_grad=%s%s" % (
+            self.n_state, self.n_ctrl, self.n_hidden, self.residual, self.activation, self.device_grad,
+            ", device_loop=True" if self.device_loop else "")
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_packed"] = {}       # a copy or an unpickled model packs into a buffer of its own
+        return state
 
     @property
     def act_code(self):
@@ -144,6 +163,27 @@ class MlpDx(torch.nn.Module):
     def device_weights(self, device):
         """(W1, b1, W2, b2) as the kernels take them - contiguous float32 on `device`; made on every call, never kept"""
         return tuple(_lib.f32c(p.detach(), device) for p in self._weights())
+
+    def packed_weights(self, device):
+        """[W1 | b1 | W2 | b2] as ONE flat float32 buffer on `device`, the `F` of `dmpc_box_ddp`'s dyn_kind 2.  The buffer is
+        kept per device and refilled in place by one launch on every call: its address is stable (a recorded hipGraph keeps
+        reading it) and an optimiser step in place is seen by the next solve - call this before every launch or replay."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        parts = [p.detach().reshape(-1) for p in self._weights()]
+        if any(p.dtype != torch.float32 or p.device != device for p in parts):
+            parts = [p.to(device=device, dtype=torch.float32) for p in parts]
+        buf = self._packed.get(device)
+        if buf is None or buf.numel() != sum(p.numel() for p in parts):
+            buf = self._packed[device] = torch.empty(sum(p.numel() for p in parts), dtype=torch.float32, device=device)
+        torch.cat(parts, out=buf)
+        return buf
+
+    def host_params(self):
+        """dyn_params of `dmpc_box_ddp`'s dyn_kind 2: (n_hidden, act, residual, search_linearizes) as floats"""
+        return (float(self.n_hidden), float(self.act_code), 1.0 if self.residual else 0.0,
+                1.0 if self.SEARCH_LINEARIZES else 0.0)
 
     def rollout_linearize(self, x_init, u, want_model=True):
         """(x [T,B,nx], F [T-1,B,nx,ns], f [T-1,B,nx]) from x_init [B,nx], u [T,B,nu] in one kernel launch

@@ -376,7 +376,20 @@ int dmpc_lin_rollout(int T, int B, int nx, int nu, const float *x_init, const fl
  *   DMPC_E_UNSUPPORTED only at T*B*(nx+nu) >= 2^31.  The pendulum at T <= 32, B % 4 == 0: ONE launch per iteration (a workgroup
  *   sweeps its four trajectories, then searches them; the first launch also rolls out and linearises) - 11-12 launches a solve;
  *   DMPC_NO_DDP_ITER_FUSED=1: 22-23, bit-identical.  The chain contains no host synchronisation and no allocation: it can be
- *   recorded in a hipGraph (batch_coupled = 0) - BoxDDP (box_ddp.py) does so by itself for a solve called again on the same buffers. */
+ *   recorded in a hipGraph (batch_coupled = 0) - BoxDDP (box_ddp.py) does so by itself for a solve called again on the same buffers.
+ * dyn_kind 2: the learned model of the MlpDx section above as the true dynamics.  F is ONE device array of contiguous
+ *   float32, 16-byte aligned, holding the packed weights [W1 (n_hidden*ns) | b1 (n_hidden) | W2 (nx*n_hidden) | b2 (nx)],
+ *   each laid out as dmpc_mlp_rollout_linearize takes it and read by every launch (nothing is cached); f must be NULL;
+ *   dyn_params = HOST array {n_hidden, act, residual, search_linearizes}: `act` the code of the MlpDx section, the last two
+ *   0 or 1.  F or dyn_params NULL, f not NULL, a negative or non-integral n_hidden / act, a flag other than 0 or 1:
+ *   DMPC_E_BADARG.  A size or activation dmpc_mlp_dx_supported refuses, or batch_coupled != 0: DMPC_E_UNSUPPORTED - as is
+ *   every dyn_kind below 0 or above 2.  All of it before the first HIP call; the workspace is dmpc_box_ddp_workspace_bytes'.
+ *   Per iteration four launches: dmpc_mlp_rollout_linearize's kernel (states and F into the workspace; f is not formed -
+ *   with need_expand the step drops it), the backward sweep of dyn_kind 0 on that F (it re-centres c itself),
+ *   dmpc_mpc_forward_rec_mlp's kernel, the bookkeeping.  search_linearizes = 1: the search also stores the Jacobians of
+ *   the trajectory it accepted - the next iteration's nominal one - so the rollout kernel runs for the first iteration
+ *   only and later iterations are three launches; both kernels evaluate the network through the same two functions on
+ *   bit-equal inputs, so every output and `state` are bit for bit those of search_linearizes = 0. */
 size_t dmpc_box_ddp_workspace_bytes(int T, int B, int nx, int nu);
 int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float *C, const float *c, const float *F,
                  const float *f, int dyn_kind, const float *dyn_params, const float *u_init, const float *u_lower,

@@ -76,6 +76,15 @@ int main() {
               const int rd = dmpc_box_ddp(T, B, nx, nu, p, p, p, nullptr, nullptr, 1, pendulum, u, p, p, 1e-3f, 5, 0.2f, 10, 1e-3f, 3, 20, 0,
                                           coupled, p, p, p, p, p, pi, ws, dwb, pi, nullptr);
               if (nx != 3 || nu != 1) EXPECT(rd == DMPC_E_BADARG);
+              // the MlpDx network inside the chain (dyn_kind 2): F = the packed weights, host floats {n_hidden, act, residual, search_linearizes}
+              for (float lin : {0.f, 1.f}) {
+                const float mlp[4] = {64.f, 2.f, 1.f, lin};
+                const int rm = dmpc_box_ddp(T, B, nx, nu, p, p, p, p, nullptr, 2, mlp, u, p, p, 1e-3f, 5, 0.2f, 10, 1e-3f, 3, 20, 0, coupled,
+                                            p, p, p, p, p, pi, ws, dwb, pi, nullptr);
+                if (coupled || nx > 16 || nu > 8) EXPECT(rm == DMPC_E_UNSUPPORTED);
+                EXPECT(dmpc_box_ddp(T, B, nx, nu, p, p, p, p, p, 2, mlp, u, p, p, 1e-3f, 5, 0.2f, 10, 1e-3f, 3, 20, 0, coupled, p, p, p, p, p,
+                                    pi, ws, dwb, pi, nullptr) == DMPC_E_BADARG);      // (f given)
+              }
             }
           }
           for (float *u : {p, p4})

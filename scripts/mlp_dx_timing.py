@@ -9,10 +9,13 @@ kernel launches of one solve of each, and how far the two solutions' costs are a
 `backward` of sum(x) + sum(u), for `MlpDx(device_grad=True)` (the gradient node's backward is `dmpc_mlp_param_grad`) and
 `device_grad=False` (a live torch rollout and autograd through it: the baseline) on equal weights in the same run.
 
+`--chain` times the iLQR loop itself: the host loop (`MlpDx(device_loop=False)`, the default route) against `dmpc_box_ddp`'s
+chain with the network inside it (`device_loop=True`: `search_linearizes` 0 and 1 launched directly, and the hipGraph replay).
+
 `--activation` picks the network (tanh, relu, silu, softplus; default tanh, whose output lines are what they were before
 the flag existed - another activation adds an "activation" key).
 
-    python scripts/mlp_dx_timing.py [--grad] [--iters 20] [--warmup 3] [--cases 3x1x32,8x2x64] [--batch 128] [--horizon 20]
+    python scripts/mlp_dx_timing.py [--grad | --chain] [--iters 20] [--warmup 3] [--cases 3x1x32,8x2x64] [--batch 128] [--horizon 20]
                                     [--activation tanh] [--json out]"""
 import argparse
 import json
@@ -81,6 +84,43 @@ def run_case(nx, nu, H, B, T, iters, warmup, activation="tanh"):
     return out
 
 
+def run_chain_case(nx, nu, H, B, T, iters, warmup, activation="tanh"):
+    """the iLQR loop four ways on equal weights in ONE run: the host loop over MPCstep objects (`device_loop=False`, the
+    default route), `dmpc_box_ddp`'s chain (dyn_kind 2) launched directly with `search_linearizes` 0 and 1, and the chain
+    replayed from the solver's hipGraph at the setting `MlpDx` passes.  Medians of device events around the whole solve
+    (host time included), the launches of one solve, and each route's costs against the host loop's."""
+    p = synthetic.make_lqr_problem(B, T, nx, nu, seed=1)
+    dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device="cuda")   # noqa: E731
+    x0, cost = dev(p["x_init"]), QuadCost(dev(p["C"]), dev(p["c"]))
+    out = dict(nx=nx, nu=nu, n_hidden=H, B=B, T=T, leg="chain", passed_search_linearizes=int(MlpDx.SEARCH_LINEARIZES))
+    if activation != "tanh":
+        out["activation"] = activation
+    sols = {}
+    # (tag, device_loop, search_linearizes or None for the class's own, graph)
+    for tag, loop, lin, graph in (("host_loop", False, None, False), ("chain_lin0", True, False, False),
+                                  ("chain_lin1", True, True, False), ("chain_graph", True, None, True)):
+        m = MlpDx(nx, nu, H, seed=0, activation=activation, device_loop=loop).cuda()
+        if lin is not None:
+            m.SEARCH_LINEARIZES = lin
+        solver = BoxDDP(T, -0.5, 0.5, B, nx, nu, None, max_iter=10, quiet=True, graph=graph)
+
+        def solve():
+            with torch.no_grad(), warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                sols[tag] = solver((x0, cost, m))
+        out[tag + "_ms"] = median_ms(solve, iters, warmup)
+        out[tag + "_launches"] = count_launches(solve)
+        out[tag + "_n_iter"], out[tag + "_status"] = solver.n_iter, solver.status
+        if graph:
+            out[tag + "_recorded"] = any(e[0] is not None for e in solver._graphs.values())
+    ch = sols["host_loop"][2]
+    for tag in ("chain_lin0", "chain_lin1", "chain_graph"):
+        out[tag + "_speedup"] = out["host_loop_ms"] / out[tag + "_ms"]
+        out[tag + "_costs_max_rel_diff"] = float(((sols[tag][2] - ch).abs() / ch.abs().clamp(min=1.0)).max())
+    out["lin1_equals_lin0"] = all(bool(torch.equal(a, b)) for a, b in zip(sols["chain_lin0"], sols["chain_lin1"]))
+    return out
+
+
 def run_grad_case(nx, nu, H, B, T, iters, warmup, activation="tanh"):
     """both routes on equal weights, alternating solve by solve; per route the median of solve + backward and of the
     backward alone (device events, host time included), the launches of one solve + backward, the sampled clocks"""
@@ -137,6 +177,7 @@ def run_grad_case(nx, nu, H, B, T, iters, warmup, activation="tanh"):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grad", action="store_true")
+    ap.add_argument("--chain", action="store_true")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--cases", default="3x1x32,8x2x64")
@@ -148,7 +189,7 @@ def main():
     res = []
     for c in a.cases.split(","):
         nx, nu, H = (int(v) for v in c.split("x"))
-        r = (run_grad_case if a.grad else run_case)(nx, nu, H, a.batch, a.horizon, max(a.iters, 20), a.warmup, a.activation)
+        r = (run_chain_case if a.chain else run_grad_case if a.grad else run_case)(nx, nu, H, a.batch, a.horizon, max(a.iters, 20), a.warmup, a.activation)
         print(json.dumps(r), flush=True)
         res.append(r)
     if a.json:
