@@ -180,6 +180,11 @@ def require_gpu():
                         "(there is no CPU fallback; the numpy oracle under oracle/ is test infrastructure)")
 
 
+def mlp_hidden2(h1, h2):
+    """DMPC_MLP_HIDDEN2 of include/dmpc.h: the `n_hidden` argument of the MlpDx entry points for two hidden layers"""
+    return int(h1) | (int(h2) << 16)
+
+
 def ptr(t):
     """device pointer of a tensor (None -> NULL); a plain int - ctypes converts it for a c_void_p parameter"""
     if t is None:

@@ -1,7 +1,8 @@
-// mlp_dx_api.hip - C-ABI entry points of the learned one-hidden-layer dynamics model (include/dmpc.h section E,
+// mlp_dx_api.hip - C-ABI entry points of the learned dynamics model with one or two hidden layers (include/dmpc.h section E,
 // "MlpDx"): the nominal rollout with its analytic linearisation, MPCstep.forward_rec with the network as the true
 // dynamics, and the gradient of the linearisation's f with respect to the weights.  Every argument and size check comes
-// before the first HIP call.  The activation is a template parameter of the kernels; mlp_with_act picks the instance.
+// before the first HIP call.  The activation and the depth are template parameters of the kernels; mlp_with_act and
+// the launchers pick the instance.  `n_hidden` is the code H1 | (H2 << 16) of DMPC_MLP_HIDDEN2 throughout.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -16,7 +17,10 @@ namespace dmpc {
 static int mlp_check(int nx, int nu, int n_hidden, int act) {
   if (nx <= 0 || nu <= 0) return DMPC_E_BADARG;
   if (act != kMlpActTanh && act != kMlpActRelu && act != kMlpActSilu && act != kMlpActSoftplus) return DMPC_E_UNSUPPORTED;
-  if (nx > kMlpMaxNx || nu > kMlpMaxNu || n_hidden < 1 || n_hidden > kMlpMaxHidden) return DMPC_E_UNSUPPORTED;
+  if (nx > kMlpMaxNx || nu > kMlpMaxNu || n_hidden < 1) return DMPC_E_UNSUPPORTED;
+  const int H1 = mlp_hidden1(n_hidden), H2 = mlp_hidden2(n_hidden);
+  if (H2 == 0 ? H1 > kMlpMaxHidden : (H1 < 1 || H1 > kMlp2MaxHidden || H2 > kMlp2MaxHidden)) return DMPC_E_UNSUPPORTED;
+  if (mlp_lds_bytes(nx, nu, H1, H2) > kMlpLdsLimit) return DMPC_E_UNSUPPORTED;
   return 0;
 }
 
@@ -31,18 +35,31 @@ static void mlp_with_act(int act, Fn &&fn) {
   }
 }
 
+// launch `kernel` with `bytes` of dynamic LDS; beyond the 64 KB a kernel has by default the limit is raised first
+template <typename K, typename... Args>
+static void mlp_launch(K kernel, int B, size_t bytes, hipStream_t stream, const Args &...args) {
+  if (bytes > 64 * 1024) set_max_lds(reinterpret_cast<const void *>(kernel), (int)bytes);
+  DMPC_LAUNCH_GGL(kernel, dim3((B + kMlpWaves - 1) / kMlpWaves), dim3(64 * kMlpWaves), bytes, stream, args...);
+}
+
 // the two launchers of mlp_dx_launch.hpp: the entry points below and dmpc_box_ddp's chain (mpc_api.hip) go through them
 void launch_mlp_rollout(const MlpRolloutArgs &a, int act, hipStream_t stream) {
+  const size_t bytes = mlp_lds_bytes(a.m.nx, a.m.nu, a.m.n_hidden, a.m.n_hidden2, a.F != nullptr);
   mlp_with_act(act, [&](auto A) {
-    DMPC_LAUNCH_GGL(mlp_rollout_linearize_kernel<decltype(A)::value>, dim3((a.B + kMlpWaves - 1) / kMlpWaves),
-                    dim3(64 * kMlpWaves), mlp_lds_bytes(a.m.nx, a.m.nu, a.m.n_hidden), stream, a);
+    constexpr int ACT = decltype(A)::value;
+    void (*kernel)(const MlpRolloutArgs) =
+        a.m.n_hidden2 > 0 ? &mlp_rollout_linearize_kernel<ACT, 2> : &mlp_rollout_linearize_kernel<ACT>;
+    mlp_launch(kernel, a.B, bytes, stream, a);
   });
 }
 
 void launch_mlp_search(const MpcFwdArgs &a, const MlpModel &m, int act, hipStream_t stream) {
+  const size_t bytes = mlp_lds_bytes(m.nx, m.nu, m.n_hidden, m.n_hidden2, a.F_next != nullptr);
   mlp_with_act(act, [&](auto A) {
-    DMPC_LAUNCH_GGL(mpc_forward_rec_mlp_kernel<decltype(A)::value>, dim3((a.B + kMlpWaves - 1) / kMlpWaves),
-                    dim3(64 * kMlpWaves), mlp_lds_bytes(m.nx, m.nu, m.n_hidden), stream, a, m);
+    constexpr int ACT = decltype(A)::value;
+    void (*kernel)(const MpcFwdArgs, const MlpModel) =
+        m.n_hidden2 > 0 ? &mpc_forward_rec_mlp_kernel<ACT, 2> : &mpc_forward_rec_mlp_kernel<ACT>;
+    mlp_launch(kernel, a.B, bytes, stream, a, m);
   });
 }
 
@@ -63,7 +80,7 @@ int dmpc_mlp_rollout_linearize(int T, int B, int nx, int nu, int n_hidden, int a
   const int rc = mlp_check(nx, nu, n_hidden, act);
   if (rc != 0) return rc;
   if ((size_t)T * B * nx * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;
-  MlpRolloutArgs ra{T, B, MlpModel{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2}, x_init, u, x_out, F_out, f_out};
+  MlpRolloutArgs ra{T, B, mlp_model(nx, nu, n_hidden, residual, W1, b1, W2, b2), x_init, u, x_out, F_out, f_out};
   launch_mlp_rollout(ra, act, static_cast<hipStream_t>(stream_));   // (no `done` flag, nothing to clear)
   return (int)hipGetLastError();
 }
@@ -83,7 +100,7 @@ int dmpc_mpc_forward_rec_mlp(int T, int B, int nx, int nu, int n_hidden, int act
   if ((size_t)T * B * (nx + nu) * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;
   MpcFwdArgs fa{T, B, Ks, ks, controls, states, u_lower, u_upper, C_true, c_true, nullptr, nullptr, ls_decay,
                 max_ls_iter, /*ls_cap=*/64, x_out, u_out, u_first, costs, old_costs, alphas, objs, n_ls_iter, info};
-  const MlpModel m{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2};
+  const MlpModel m = mlp_model(nx, nu, n_hidden, residual, W1, b1, W2, b2);
   launch_mlp_search(fa, m, act, static_cast<hipStream_t>(stream_));  // (fa.done, fa.F_next: nullptr)
   return (int)hipGetLastError();
 }
@@ -91,7 +108,7 @@ int dmpc_mpc_forward_rec_mlp(int T, int B, int nx, int nu, int n_hidden, int act
 int dmpc_mlp_param_grad_partials(int B) { return B > 0 ? mlp_grad_partials(B) : 0; }
 
 size_t dmpc_mlp_param_grad_workspace_bytes(int B, int nx, int nu, int n_hidden) {
-  if (B <= 0 || mlp_check(nx, nu, n_hidden, 0) != 0) return 0;
+  if (B <= 0 || mlp_check(nx, nu, n_hidden, 0) != 0 || mlp_hidden2(n_hidden) != 0) return 0;   // (one hidden layer only)
   return (size_t)mlp_grad_partials(B) * mlp_grad_partial_floats(nx, nu, n_hidden) * sizeof(float);
 }
 
@@ -104,6 +121,7 @@ int dmpc_mlp_param_grad(int T, int B, int nx, int nu, int n_hidden, int act, int
   if (T > 1 && !grad_f) return DMPC_E_BADARG;
   const int rc = mlp_check(nx, nu, n_hidden, act);
   if (rc != 0) return rc;
+  if (mlp_hidden2(n_hidden) != 0) return DMPC_E_UNSUPPORTED;   // two hidden layers: the weight gradient is the live route's
   if ((size_t)T * B * nx * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;   // (the rollout's own limit)
   if (T > 1 && (ws == nullptr || ws_bytes < dmpc_mlp_param_grad_workspace_bytes(B, nx, nu, n_hidden))) return DMPC_E_WORKSPACE;
   hipStream_t stream = static_cast<hipStream_t>(stream_);

@@ -1,9 +1,12 @@
-// mlp_dx_kernels.hpp - a learned one-hidden-layer dynamics model on the device (MlpDx of the Python layer):
+// mlp_dx_kernels.hpp - a learned dynamics model with one or two hidden layers on the device (MlpDx of the Python layer):
 //
-//     next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual),     act = tanh | relu | silu | softplus
+//     depth 1:  next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual),     act = tanh | relu | silu | softplus
+//     depth 2:  next(x, u) = W3 act(W2 act(W1 [x;u] + b1) + b2) + b3 (+ x when residual)
 //
 // The activation is a template parameter of the three kernels that evaluate the network (mlp_act below is the only place
-// where it is looked at): a = act(z) and d = act'(z) of the pre-activation z = W1 [x;u] + b1.
+// where it is looked at): a = act(z) and d = act'(z) of the pre-activation z = W1 [x;u] + b1.  The depth is a second
+// template parameter of the rollout and the search (MlpNet<DEPTH> below); the depth-one instances run the functions they
+// ran before the second depth existed.  The two-layer network is described behind the one-layer functions ("Depth two").
 //
 //   mlp_rollout_linearize_kernel   get_traj + linearize_dynamics (util.py:239-277, mpc/approximate.py:77-119) in one
 //                                  launch: x_{t+1} = next(x_t, u_t), F_t = [I|0] residual + W2 diag(d) W1,
@@ -57,9 +60,23 @@ struct MlpLds {
 __host__ __device__ inline int mlp_lds_floats(int nx, int nu, int H) {
   return H * ((nx + nu) | 1) + nx * (H | 1) + H + nx;
 }
-inline size_t mlp_lds_bytes(int nx, int nu, int H) {
-  return (size_t)(mlp_lds_floats(nx, nu, H) + kMlpWaves * kMlpWaveFloats) * sizeof(float);
+
+// depth two: H1, H2 <= 128, so a lane owns at most two units of either layer
+constexpr int kMlp2MaxHidden = 128;
+constexpr int kMlp2Units = kMlp2MaxHidden / 64;
+// a wavefront's own floats: d1 and d2 per hidden unit, N = W3 D2 W2 with an odd row stride, the step's Jacobian
+constexpr int kMlp2WaveFloats = 2 * kMlp2MaxHidden + kMlpMaxNx * (kMlp2MaxHidden | 1) + kMlpMaxNx * (kMlpMaxNx + kMlpMaxNu);
+__host__ __device__ inline int mlp2_lds_floats(int nx, int nu, int H1, int H2) {
+  return H1 * ((nx + nu) | 1) + H2 * (H1 | 1) + nx * (H2 | 1) + H1 + H2 + nx;
 }
+
+// THE byte count of a launch's dynamic LDS, for the launchers and for dmpc_mlp_dx_supported.  H2 = 0: one hidden layer.
+// `jacobian`: the launch forms F (depth one always has its slices: its instances are what they were).
+inline size_t mlp_lds_bytes(int nx, int nu, int H1, int H2 = 0, bool jacobian = true) {
+  if (H2 == 0) return (size_t)(mlp_lds_floats(nx, nu, H1) + kMlpWaves * kMlpWaveFloats) * sizeof(float);
+  return (size_t)(mlp2_lds_floats(nx, nu, H1, H2) + (jacobian ? kMlpWaves * kMlp2WaveFloats : 0)) * sizeof(float);
+}
+constexpr size_t kMlpLdsLimit = 160 * 1024;   // a gfx950 CU's LDS: one workgroup of the largest two-layer model
 
 __device__ __forceinline__ float lane_value(float v, int l) {   // l is wave-uniform
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
@@ -195,14 +212,230 @@ __device__ __forceinline__ void mlp_jacobian_store(const MlpModel &m, const MlpL
   if (fq != nullptr && lane < nx) fq[lane] = f;
 }
 
+// ---------------------------------------------------------------------------------------------------- Depth two
+// The same layout: one wavefront per trajectory, four per workgroup, the weights staged once and one barrier.
+//     W1s [H1][ns | 1]   as above
+//     W2s [H2][H1 | 1]   lane l owns units l, l + 64 of layer 2 and walks ITS row: 64 rows on 64 banks
+//     W3s [nx][H2 | 1]   as W2s above
+//     b1s [H1], b2s [H2], b3s [nx]
+// 88.2 KB at the limits (nx 16, nu 8, H1 = H2 = 128).  A launch that forms Jacobians adds kMlp2WaveFloats (10.8 KB) per
+// wavefront: 131.5 KB, one workgroup per CU.  A layer-1 activation another lane needs is read from that lane's register
+// (v_readlane), so the step function touches no wavefront slice and the search without Jacobians has none.
+struct Mlp2Lds {
+  int nsp, hp1, hp2;                // row strides of W1s, W2s (and N) and W3s
+  float *W1s, *W2s, *W3s, *b1s, *b2s, *b3s, *wave;
+};
+
+__device__ __forceinline__ Mlp2Lds mlp2_stage(const MlpModel &m, float *lds) {
+  const int ns = m.nx + m.nu, H1 = m.n_hidden, H2 = m.n_hidden2;
+  Mlp2Lds L;
+  L.nsp = ns | 1;
+  L.hp1 = H1 | 1;
+  L.hp2 = H2 | 1;
+  L.W1s = lds;
+  L.W2s = L.W1s + H1 * L.nsp;
+  L.W3s = L.W2s + H2 * L.hp1;
+  L.b1s = L.W3s + m.nx * L.hp2;
+  L.b2s = L.b1s + H1;
+  L.b3s = L.b2s + H2;
+  L.wave = L.b3s + m.nx + (threadIdx.x / 64) * kMlp2WaveFloats;   // (only a launch that forms Jacobians has it)
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int e = tid; e < H1 * ns; e += nt) L.W1s[(e / ns) * L.nsp + (e % ns)] = m.W1[e];
+  for (int e = tid; e < H2 * H1; e += nt) L.W2s[(e / H1) * L.hp1 + (e % H1)] = m.W2[e];
+  for (int e = tid; e < m.nx * H2; e += nt) L.W3s[(e / H2) * L.hp2 + (e % H2)] = m.W3[e];
+  for (int e = tid; e < H1; e += nt) L.b1s[e] = m.b1[e];
+  for (int e = tid; e < H2; e += nt) L.b2s[e] = m.b2[e];
+  for (int e = tid; e < m.nx; e += nt) L.b3s[e] = m.b3[e];
+  __syncthreads();
+  return L;
+}
+
+// ONE step of the two-layer model, the only place it is evaluated.  As mlp_next: explicit fmaf; layer-1 inputs ascending,
+// layer-2 inputs (the hidden units of layer 1) ascending, a lane's units ascending, one butterfly reduction per output;
+// units beyond H1 / H2 hold exact zeros and read clamped addresses.  Leaves this lane's act' of both layers in d1[], d2[].
+template <int ACT>
+__device__ __forceinline__ float mlp2_next(const MlpModel &m, const Mlp2Lds &L, const int lane, const float tau,
+                                           float (&d1)[kMlp2Units], float (&d2)[kMlp2Units]) {
+  const int ns = m.nx + m.nu, H1 = m.n_hidden, H2 = m.n_hidden2;
+  const int n1 = (H1 + 63) / 64, n2 = (H2 + 63) / 64;
+  int row1[kMlp2Units], row2[kMlp2Units];
+  bool has1[kMlp2Units], has2[kMlp2Units];
+  float z1[kMlp2Units], z2[kMlp2Units], a1[kMlp2Units], a2[kMlp2Units];
+#pragma unroll
+  for (int k = 0; k < kMlp2Units; ++k) {
+    const int h = lane + 64 * k;
+    has1[k] = h < H1;
+    row1[k] = has1[k] ? h : H1 - 1;
+    z1[k] = has1[k] ? L.b1s[row1[k]] : 0.f;
+    has2[k] = h < H2;
+    row2[k] = has2[k] ? h : H2 - 1;
+    z2[k] = has2[k] ? L.b2s[row2[k]] : 0.f;
+  }
+  for (int j = 0; j < ns; ++j) {
+    const float tj = lane_value(tau, j);
+#pragma unroll
+    for (int k = 0; k < kMlp2Units; ++k) {
+      if (k < n1) {
+        const float w = L.W1s[row1[k] * L.nsp + j];
+        z1[k] = fmaf(has1[k] ? w : 0.f, tj, z1[k]);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kMlp2Units; ++k) {
+    float ak, dk;
+    mlp_act<ACT>(z1[k], ak, dk);
+    const bool live = k < n1 && has1[k];
+    a1[k] = live ? ak : 0.f;
+    d1[k] = live ? dk : 0.f;
+  }
+#pragma unroll
+  for (int k1 = 0; k1 < kMlp2Units; ++k1) {        // unit h = 64 k1 + l of layer 1 lives in a1[k1] of lane l
+    const int left = H1 - 64 * k1, cnt = left < 64 ? left : 64;
+    for (int l = 0; l < cnt; ++l) {
+      const float ah = lane_value(a1[k1], l);
+#pragma unroll
+      for (int k = 0; k < kMlp2Units; ++k) {
+        if (k < n2) {
+          const float w = L.W2s[row2[k] * L.hp1 + 64 * k1 + l];
+          z2[k] = fmaf(has2[k] ? w : 0.f, ah, z2[k]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kMlp2Units; ++k) {
+    float ak, dk;
+    mlp_act<ACT>(z2[k], ak, dk);
+    const bool live = k < n2 && has2[k];
+    a2[k] = live ? ak : 0.f;
+    d2[k] = live ? dk : 0.f;
+  }
+  float next = 0.f;
+  for (int i = 0; i < m.nx; ++i) {
+    float part = 0.f;
+#pragma unroll
+    for (int k = 0; k < kMlp2Units; ++k) {
+      if (k < n2) {
+        const float w = L.W3s[i * L.hp2 + row2[k]];
+        part = fmaf(has2[k] ? w : 0.f, a2[k], part);
+      }
+    }
+    float s = wave_sum64(part) + L.b3s[i];
+    if (m.residual) s += lane_value(tau, i);
+    next = lane == i ? s : next;
+  }
+  return next;
+}
+
+// F = [I|0] residual + W3 D2 W2 D1 W1 at Fp, f = next - F tau at fq (lanes < nx).  VALU over LDS, in two products through the
+// wavefront's slice, every sum over hidden units ascending:
+//   N = W3 D2 W2 (nx x H1): a lane owns columns lane, lane + 64 and takes the rows four at a time - per unit of layer 2 one
+//       d2, the lane's two W2 entries (consecutive lanes, consecutive words) and four W3 entries (one word for the wavefront)
+//       feed eight fused multiply-adds;
+//   F = N D1 W1 + [I|0]: lane e owns entries e, e + 64, ... as in mlp_jacobian_store.
+__device__ __forceinline__ void mlp2_jacobian_store(const MlpModel &m, const Mlp2Lds &L, const int lane, const float tau,
+                                                    const float next, const float (&d1)[kMlp2Units],
+                                                    const float (&d2)[kMlp2Units], float *Fp, float *fq) {
+  const int nx = m.nx, ns = m.nx + m.nu, H1 = m.n_hidden, H2 = m.n_hidden2;
+  const int n1 = (H1 + 63) / 64;
+  float *g1 = L.wave, *g2 = g1 + kMlp2MaxHidden, *Ns = g2 + kMlp2MaxHidden, *Fs = Ns + kMlpMaxNx * (kMlp2MaxHidden | 1);
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the previous step's reads of the slice are done)
+  int col[kMlp2Units];
+  bool has[kMlp2Units];
+#pragma unroll
+  for (int k = 0; k < kMlp2Units; ++k) {
+    const int h = lane + 64 * k;
+    has[k] = h < H1;
+    col[k] = has[k] ? h : H1 - 1;
+    if (h < H1) g1[h] = d1[k];
+    if (h < H2) g2[h] = d2[k];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  for (int i0 = 0; i0 < nx; i0 += 4) {
+    int r[4];
+    float acc[kMlp2Units][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      r[q] = (i0 + q < nx ? i0 + q : nx - 1) * L.hp2;
+#pragma unroll
+      for (int k = 0; k < kMlp2Units; ++k) acc[k][q] = 0.f;
+    }
+    for (int h = 0; h < H2; ++h) {
+      const float dd = g2[h];
+      float w2[kMlp2Units];
+#pragma unroll
+      for (int k = 0; k < kMlp2Units; ++k) w2[k] = k < n1 ? L.W2s[h * L.hp1 + col[k]] : 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float w3d = L.W3s[r[q] + h] * dd;
+#pragma unroll
+        for (int k = 0; k < kMlp2Units; ++k) acc[k][q] = fmaf(w3d, w2[k], acc[k][q]);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int k = 0; k < kMlp2Units; ++k)
+        if (i0 + q < nx && k < n1 && has[k]) Ns[(i0 + q) * L.hp1 + col[k]] = acc[k][q];
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  for (int e = lane; e < nx * ns; e += 64) {
+    const int i = e / ns, j = e % ns;
+    const float *nr = Ns + i * L.hp1, *w1 = L.W1s + j;
+    float acc = (m.residual && i == j) ? 1.f : 0.f;
+#pragma unroll 4
+    for (int h = 0; h < H1; ++h) acc = fmaf(nr[h] * g1[h], w1[h * L.nsp], acc);
+    Fs[e] = acc;
+    Fp[e] = acc;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  const int rr = lane < nx ? lane : 0;
+  float f = next;
+  for (int j = 0; j < ns; ++j) f = fmaf(-Fs[rr * ns + j], lane_value(tau, j), f);
+  if (fq != nullptr && lane < nx) fq[lane] = f;
+}
+
+// What the rollout and the search know of a network's depth: how its weights are staged, ONE step, that step's Jacobian.
+template <int DEPTH>
+struct MlpNet;
+template <>
+struct MlpNet<1> {
+  using Lds = MlpLds;
+  float a[kMlpUnits], d[kMlpUnits];
+  static __device__ __forceinline__ Lds stage(const MlpModel &m, float *lds) { return mlp_stage(m, lds); }
+  template <int ACT>
+  __device__ __forceinline__ float next(const MlpModel &m, const Lds &L, const int lane, const float tau) {
+    return mlp_next<ACT>(m, L, lane, tau, a, d);
+  }
+  __device__ __forceinline__ void jacobian_store(const MlpModel &m, const Lds &L, const int lane, const float tau,
+                                                 const float xn, float *Fp, float *fq) const {
+    mlp_jacobian_store(m, L, lane, tau, xn, d, Fp, fq);
+  }
+};
+template <>
+struct MlpNet<2> {
+  using Lds = Mlp2Lds;
+  float d1[kMlp2Units], d2[kMlp2Units];
+  static __device__ __forceinline__ Lds stage(const MlpModel &m, float *lds) { return mlp2_stage(m, lds); }
+  template <int ACT>
+  __device__ __forceinline__ float next(const MlpModel &m, const Lds &L, const int lane, const float tau) {
+    return mlp2_next<ACT>(m, L, lane, tau, d1, d2);
+  }
+  __device__ __forceinline__ void jacobian_store(const MlpModel &m, const Lds &L, const int lane, const float tau,
+                                                 const float xn, float *Fp, float *fq) const {
+    mlp2_jacobian_store(m, L, lane, tau, xn, d1, d2, Fp, fq);
+  }
+};
+
 // (MlpRolloutArgs: mlp_dx_launch.hpp.)  In a box-DDP chain: a.clear runs first - thread g of the grid zeroes word g of each
 // range, and the grid has at least max(B, 256) threads - and a set `done` flag ends the launch before its barrier.
-template <int ACT>
-__global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(const MlpRolloutArgs a) {
-  extern __shared__ float lds[];
+template <int ACT, int DEPTH>
+__device__ __forceinline__ void mlp_rollout_linearize_body(const MlpRolloutArgs &a, float *lds) {
   a.clear.run(blockIdx.x * blockDim.x + threadIdx.x);
   if (a.done != nullptr && *a.done != 0) return;   // grid-uniform: the iLQR loop has stopped
-  const MlpLds L = mlp_stage(a.m, lds);
+  const typename MlpNet<DEPTH>::Lds L = MlpNet<DEPTH>::stage(a.m, lds);
   const int lane = threadIdx.x % 64;
   const int b = blockIdx.x * kMlpWaves + threadIdx.x / 64;
   if (b >= a.B) return;      // (after the only barrier) a wavefront without a trajectory stores nothing
@@ -215,11 +448,26 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(c
     if (lane < nx) a.x[tb * nx + lane] = xc;
     if (t == T - 1) break;
     const float tau = lane < nx ? xc : (lane < ns ? a.u[tb * nu + (lane - nx)] : 0.f);
-    float act[kMlpUnits], dact[kMlpUnits];
-    const float xn = mlp_next<ACT>(a.m, L, lane, tau, act, dact);
-    if (a.F != nullptr) mlp_jacobian_store(a.m, L, lane, tau, xn, dact, a.F + tb * nx * ns, a.f ? a.f + tb * nx : nullptr);
+    MlpNet<DEPTH> net;
+    const float xn = net.template next<ACT>(a.m, L, lane, tau);
+    if (a.F != nullptr) net.jacobian_store(a.m, L, lane, tau, xn, a.F + tb * nx * ns, a.f ? a.f + tb * nx : nullptr);
     xc = xn;
   }
+}
+
+// The kernels.  The depth is the second template parameter; the depth-one instances keep the one-parameter names they had
+// before the second depth existed (profilers' lists and the recorded search values name them), so each kernel is a pair of
+// overloaded templates over one body.
+template <int ACT>
+__global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(const MlpRolloutArgs a) {
+  extern __shared__ float lds[];
+  mlp_rollout_linearize_body<ACT, 1>(a, lds);
+}
+template <int ACT, int DEPTH>
+__global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(const MlpRolloutArgs a) {
+  static_assert(DEPTH == 2, "the depth-one kernel is mlp_rollout_linearize_kernel<ACT>");
+  extern __shared__ float lds[];
+  mlp_rollout_linearize_body<ACT, DEPTH>(a, lds);
 }
 
 // forward_rec: the arithmetic of a pass, its order and the search's decisions are mpc_generic_forward_kernel's (and
@@ -229,11 +477,11 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(c
 // a.F_next (BoxDDP's chain): the accepted trajectory IS the next iteration's nominal one, so after the search the wavefront
 // walks it once more and stores its Jacobians, F_next [T-1,B,nx,ns] - through mlp_next and mlp_jacobian_store on the values
 // mlp_rollout_linearize_kernel would start from, hence bit for bit what that kernel would store.  a.f_next, a.c_next: not written.
-template <int ACT>
-__global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(const MpcFwdArgs a, const MlpModel m) {
-  extern __shared__ float lds[];
+// Depth two: the wavefront slices exist only when a.F_next is given (mlp_lds_bytes).
+template <int ACT, int DEPTH>
+__device__ __forceinline__ void mpc_forward_rec_mlp_body(const MpcFwdArgs &a, const MlpModel &m, float *lds) {
   if (a.done != nullptr && *a.done != 0) return;   // grid-uniform, before the barrier: the iLQR loop has stopped
-  const MlpLds L = mlp_stage(m, lds);
+  const typename MlpNet<DEPTH>::Lds L = MlpNet<DEPTH>::stage(m, lds);
   const int lane = threadIdx.x % 64;
   const int b = blockIdx.x * kMlpWaves + threadIdx.x / 64;
   if (b >= a.B) return;      // (after the only barrier)
@@ -295,8 +543,8 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(con
       if (first) old_cost += wave_sum64(part0);                                          // :191
       if (a.objs != nullptr && lane == 0) a.objs[tb] = obj;
       if (t < T - 1) {                                                                   // :237-240
-        float act[kMlpUnits], dact[kMlpUnits];
-        xc = mlp_next<ACT>(m, L, lane, tau, act, dact);
+        MlpNet<DEPTH> net;
+        xc = net.template next<ACT>(m, L, lane, tau);
       }
     }
     ls.advance(delta, a.ls_decay);
@@ -312,12 +560,24 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(con
       const size_t tb = (size_t)t * B + b;
       const float v = a.u[tb * nu + mu];
       const float tau = is_x ? xc : (is_u ? v : 0.f);
-      float act[kMlpUnits], dact[kMlpUnits];
-      const float xn = mlp_next<ACT>(m, L, lane, tau, act, dact);
-      mlp_jacobian_store(m, L, lane, tau, xn, dact, a.F_next + tb * nx * ns, nullptr);
+      MlpNet<DEPTH> net;
+      const float xn = net.template next<ACT>(m, L, lane, tau);
+      net.jacobian_store(m, L, lane, tau, xn, a.F_next + tb * nx * ns, nullptr);
       xc = xn;
     }
   }
+}
+
+template <int ACT>
+__global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(const MpcFwdArgs a, const MlpModel m) {
+  extern __shared__ float lds[];
+  mpc_forward_rec_mlp_body<ACT, 1>(a, m, lds);
+}
+template <int ACT, int DEPTH>
+__global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(const MpcFwdArgs a, const MlpModel m) {
+  static_assert(DEPTH == 2, "the depth-one kernel is mpc_forward_rec_mlp_kernel<ACT>");
+  extern __shared__ float lds[];
+  mpc_forward_rec_mlp_body<ACT, DEPTH>(a, m, lds);
 }
 
 // The gradient of L(f) with respect to W1, b1, W2, b2 for f_t = next(x_t, u_t) - F_t [x_t;u_t] along the rolled states,

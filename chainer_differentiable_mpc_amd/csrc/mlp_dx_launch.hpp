@@ -10,15 +10,39 @@
 
 namespace dmpc {
 
+// One hidden layer (n_hidden2 == 0):  next = W2 act(W1 [x;u] + b1) + b2 (+ x), W2 [nx,H1].
+// Two (n_hidden2 = H2 >= 1):          next = W3 act(W2 act(W1 [x;u] + b1) + b2) + b3 (+ x), W2 [H2,H1], W3 [nx,H2].
 struct MlpModel {
   int nx, nu, n_hidden, residual;
-  const float *W1, *b1, *W2, *b2;   // [H,ns], [H], [nx,H], [nx]  (device pointers: an optimiser step is seen by the next launch)
+  const float *W1, *b1, *W2, *b2;   // [H1,ns], [H1], W2, its bias  (device pointers: an optimiser step is seen by the next launch)
+  int n_hidden2 = 0;
+  const float *W3 = nullptr, *b3 = nullptr;
 };
 
-// the weights as ONE array [W1 | b1 | W2 | b2] (dmpc_box_ddp, dyn_kind 2)
-inline MlpModel mlp_model_packed(int nx, int nu, int n_hidden, int residual, const float *packed) {
-  const float *b1 = packed + (size_t)n_hidden * (nx + nu), *W2 = b1 + n_hidden, *b2 = W2 + (size_t)nx * n_hidden;
-  return MlpModel{nx, nu, n_hidden, residual != 0 ? 1 : 0, packed, b1, W2, b2};
+// The `n_hidden` argument of the C ABI is H1 | (H2 << 16) (DMPC_MLP_HIDDEN2 of include/dmpc.h); H2 = 0: one hidden layer.
+inline int mlp_hidden1(int code) { return code & 0xffff; }
+inline int mlp_hidden2(int code) { return code >> 16; }
+
+// the model as the C ABI passes it: for two layers W2 points to [W2 (H2*H1) | W3 (nx*H2)] and b2 to [b2 (H2) | b3 (nx)]
+inline MlpModel mlp_model(int nx, int nu, int code, int residual, const float *W1, const float *b1, const float *W2,
+                          const float *b2) {
+  const int H1 = mlp_hidden1(code), H2 = mlp_hidden2(code);
+  MlpModel m{nx, nu, H1, residual != 0 ? 1 : 0, W1, b1, W2, b2};
+  if (H2 > 0) {
+    m.n_hidden2 = H2;
+    m.W3 = W2 + (size_t)H2 * H1;
+    m.b3 = b2 + H2;
+  }
+  return m;
+}
+
+// the weights as ONE array (dmpc_box_ddp, dyn_kind 2): [W1 | b1 | W2 | b2], or [W1 | b1 | W2 | W3 | b2 | b3] - the tails
+// behind b1 are then what mlp_model takes as W2 and b2
+inline MlpModel mlp_model_packed(int nx, int nu, int code, int residual, const float *packed) {
+  const int H1 = mlp_hidden1(code), H2 = mlp_hidden2(code);
+  const float *b1 = packed + (size_t)H1 * (nx + nu), *W2 = b1 + H1;
+  const float *b2 = W2 + (H2 > 0 ? (size_t)H2 * H1 + (size_t)nx * H2 : (size_t)nx * H1);
+  return mlp_model(nx, nu, code, residual, packed, b1, W2, b2);
 }
 
 struct MlpRolloutArgs {
@@ -30,8 +54,8 @@ struct MlpRolloutArgs {
   ChainClear clear;                // first launch of a box-DDP chain: words to zero (loop state, meeting words, flags)
 };
 
-// mlp_rollout_linearize_kernel<act> / mpc_forward_rec_mlp_kernel<act> on `stream`, for sizes and an `act` that
-// dmpc_mlp_dx_supported has passed.  The search writes the accepted trajectory's Jacobians when a.F_next is given.
+// mlp_rollout_linearize_kernel<act, depth> / mpc_forward_rec_mlp_kernel<act, depth> on `stream`, for sizes and an `act` that
+// dmpc_mlp_dx_supported has passed; the depth is the model's.  The search writes the accepted trajectory's Jacobians when a.F_next is given.
 void launch_mlp_rollout(const MlpRolloutArgs &a, int act, hipStream_t stream);
 void launch_mlp_search(const MpcFwdArgs &a, const MlpModel &m, int act, hipStream_t stream);
 

@@ -993,14 +993,15 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   if (dyn_kind == 0 && !F) return DMPC_E_BADARG;
   if (dyn_kind == 1 && (!dyn_params || nx != 3 || nu != 1)) return DMPC_E_BADARG;
   if (dyn_kind < 0 || dyn_kind > 2) return DMPC_E_UNSUPPORTED;
-  // MlpDx: F is the packed weights, dyn_params = {n_hidden, act, residual, search_linearizes} on the host
+  // MlpDx: F is the packed weights, dyn_params = {n_hidden, act, residual, search_linearizes} on the host; n_hidden is the
+  // code H1 | (H2 << 16) as an integral float (exact: it stays below 2^24)
   int mlp_hidden = 0, mlp_act = 0, mlp_residual = 0, mlp_search_lin = 0;
   if (dyn_kind == 2) {
     if (!F || f != nullptr || !dyn_params) return DMPC_E_BADARG;
     const float h = dyn_params[0], ac = dyn_params[1], res = dyn_params[2], sl = dyn_params[3];
     if (!(h >= 0.f) || h != floorf(h) || !(ac >= 0.f) || ac != floorf(ac)) return DMPC_E_BADARG;   // (a NaN fails `>=`)
     if ((res != 0.f && res != 1.f) || (sl != 0.f && sl != 1.f)) return DMPC_E_BADARG;
-    mlp_hidden = h > 1e6f ? 1000000 : (int)h;
+    mlp_hidden = h >= 16777216.f ? 0 : (int)h;   // (0: no size the kernels serve)
     mlp_act = ac > 1e6f ? 1000000 : (int)ac;
     mlp_residual = res != 0.f;
     mlp_search_lin = sl != 0.f;

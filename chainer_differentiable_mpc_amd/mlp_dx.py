@@ -1,11 +1,14 @@
-"""`MlpDx` - a learned one-hidden-layer dynamics model for `BoxDDP` / `MPCstep`:
+"""`MlpDx` - a learned dynamics model with one or two hidden layers for `BoxDDP` / `MPCstep`:
 
-    next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual),     act = tanh (the default), relu, silu or softplus
+    n_hidden = H:         next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual)
+    n_hidden = (H1, H2):  next(x, u) = W3 act(W2 act(W1 [x;u] + b1) + b2) + b3 (+ x when residual)
 
-`MlpDx.from_sequential` takes the weights of a `torch.nn.Sequential(Linear, act, Linear)` trained elsewhere.
+act = tanh (the default), relu, silu or softplus, the same in both layers.  `MlpDx.from_sequential` takes the weights of a
+`torch.nn.Sequential(Linear, act, Linear)` trained elsewhere; the six tensors of a two-layer network are copied into
+`W1, b1, W2, b2, W3, b3` by hand.
 
-`forward` is torch code (CPU and GPU tensors).  On the GPU, at a size the kernels serve (nx <= 16, nu <= 8, n_hidden <= 256),
-the nominal rollout with its analytic linearisation is one launch (`dmpc_mlp_rollout_linearize`) and `MPCstep`'s line search
+`forward` is torch code (CPU and GPU tensors).  On the GPU, at a size the kernels serve (nx <= 16, nu <= 8, and H <= 256 or
+H1, H2 <= 128), the nominal rollout with its analytic linearisation is one launch (`dmpc_mlp_rollout_linearize`) and `MPCstep`'s line search
 evaluates the network inside its kernel (`dmpc_mpc_forward_rec_mlp`); the hooks are the ones `PendulumDx` has (`linearize`,
 `fused_ok`, `rollout_linearize`).  The weights go to the library as device pointers on every call: nothing is read back and
 nothing is cached, so an optimiser step in place is seen by the next call.
@@ -15,9 +18,9 @@ instead (`dmpc_box_ddp`, dyn_kind 2: the weights as one packed buffer, `packed_w
 GPU tensors, a supported size, a dense `QuadCost`, no `batch_coupled`; anything else keeps the host loop.
 
 Learning the weights follows mpc/approximate.py:77-119: the Jacobians F_t are constants of the graph, f_t = next - F_t [x;u]
-stays on it through `next` and the re-rolled states, and `MPCstep.backward`'s df reaches W1, b1, W2, b2.  By default that
-graph is a live torch rollout; with `device_grad=True` it is one autograd node around the rollout's launch whose backward
-is `dmpc_mlp_param_grad` (one sweep kernel, one fixed-order reduction)."""
+stays on it through `next` and the re-rolled states, and `MPCstep.backward`'s df reaches every weight.  By default that
+graph is a live torch rollout; with `device_grad=True` (one hidden layer only) it is one autograd node around the rollout's
+launch whose backward is `dmpc_mlp_param_grad` (one sweep kernel, one fixed-order reduction)."""
 import math
 
 import torch
@@ -60,21 +63,54 @@ class MlpDx(torch.nn.Module):
         # BoxDDP runs its iLQR loop as one chain of launches (`dmpc_box_ddp`, dyn_kind 2) where the chain serves the problem
         self.device_loop = bool(device_loop)
         self._packed = {}           # device -> the flat weight buffer of `packed_weights` (no parameter, no buffer, not pickled)
-        self.n_state, self.n_ctrl, self.n_hidden = int(n_state), int(n_ctrl), int(n_hidden)
+        self.n_state, self.n_ctrl = int(n_state), int(n_ctrl)
+        # `hidden`: the widths as a tuple of one or two; `n_hidden` is what the caller gave - an int, or the pair
+        if isinstance(n_hidden, (tuple, list)):
+            if len(n_hidden) != 2:
+                raise ValueError("MlpDx: n_hidden is an int or a pair (H1, H2), found %r" % (n_hidden,))
+            self.hidden = (int(n_hidden[0]), int(n_hidden[1]))
+            self.n_hidden = self.hidden
+        else:
+            self.n_hidden = int(n_hidden)
+            self.hidden = (self.n_hidden,)
+        if min(self.hidden) < 1:
+            raise ValueError("MlpDx: every hidden layer needs at least one unit, found %r" % (n_hidden,))
+        if self.depth == 2 and self.device_grad:
+            raise ValueError("MlpDx: device_grad=True serves one hidden layer only (dmpc_mlp_param_grad); a model with two "
+                             "takes its weight gradient from the default live route")
         self.residual = bool(residual)
         ns = self.n_state + self.n_ctrl
         gen = None if seed is None else torch.Generator().manual_seed(int(seed))
-        self.W1 = torch.nn.Parameter(0.5 * torch.randn(self.n_hidden, ns, generator=gen) / math.sqrt(ns))
-        self.b1 = torch.nn.Parameter(torch.zeros(self.n_hidden))
-        self.W2 = torch.nn.Parameter(0.5 * torch.randn(self.n_state, self.n_hidden, generator=gen) / math.sqrt(self.n_hidden))
-        self.b2 = torch.nn.Parameter(torch.zeros(self.n_state))
+        H1, out = self.hidden[0], self.n_state
+        self.W1 = torch.nn.Parameter(0.5 * torch.randn(H1, ns, generator=gen) / math.sqrt(ns))
+        self.b1 = torch.nn.Parameter(torch.zeros(H1))
+        if self.depth == 2:
+            H2 = self.hidden[1]
+            self.W2 = torch.nn.Parameter(torch.randn(H2, H1, generator=gen) / math.sqrt(H1))
+            self.b2 = torch.nn.Parameter(torch.zeros(H2))
+            self.W3 = torch.nn.Parameter(0.5 * torch.randn(out, H2, generator=gen) / math.sqrt(H2))
+            self.b3 = torch.nn.Parameter(torch.zeros(out))
+        else:
+            self.W2 = torch.nn.Parameter(0.5 * torch.randn(out, H1, generator=gen) / math.sqrt(H1))
+            self.b2 = torch.nn.Parameter(torch.zeros(out))
         self._size_ok = None
+
+    @property
+    def depth(self):
+        """the number of hidden layers, 1 or 2"""
+        return len(self.hidden)
+
+    @property
+    def hidden_code(self):
+        """the `n_hidden` argument of the C ABI: H, or DMPC_MLP_HIDDEN2(H1, H2)"""
+        return self.hidden[0] if self.depth == 1 else _lib.mlp_hidden2(*self.hidden)
 
     @classmethod
     def from_sequential(cls, net, n_state, n_ctrl, residual=True, device_grad=False, device_loop=False):
         """the model of a trained `torch.nn.Sequential(Linear(n_state + n_ctrl, H), act, Linear(H, n_state))` whose input is
         [x;u], act one of Tanh, ReLU, SiLU, Softplus (beta = 1, threshold = 20).  The four tensors are copied; anything else is
-        a ValueError that names what was found."""
+        a ValueError that names what was found - a deeper network too: for two hidden layers construct
+        `MlpDx(n_state, n_ctrl, (H1, H2), activation=...)` and copy the six tensors into W1, b1, W2, b2, W3, b3."""
         n_state, n_ctrl = int(n_state), int(n_ctrl)
         found = "Sequential(%s)" % ", ".join(repr(m) for m in net) if isinstance(net, torch.nn.Sequential) else repr(net)
         if not isinstance(net, torch.nn.Sequential) or len(net) != 3:
@@ -100,7 +136,7 @@ class MlpDx(torch.nn.Module):
         return m.to(device=l1.weight.device, dtype=l1.weight.dtype)
 
     def extra_repr(self):
-        return "n_state=%d, n_ctrl=%d, n_hidden=%d, residual=%s, activation=%s, device_grad=%s%s" % (
+        return "n_state=%d, n_ctrl=%d, n_hidden=%s, residual=%s, activation=%s, device_grad=%s%s" % (
             self.n_state, self.n_ctrl, self.n_hidden, self.residual, self.activation, self.device_grad,
             ", device_loop=True" if self.device_loop else "")
 
@@ -115,28 +151,45 @@ class MlpDx(torch.nn.Module):
         return ACTIVATIONS[self.activation]
 
     def _weights(self):
+        """the parameters layer by layer: (W1, b1, W2, b2) or (W1, b1, W2, b2, W3, b3)"""
+        if self.depth == 2:
+            return self.W1, self.b1, self.W2, self.b2, self.W3, self.b3
         return self.W1, self.b1, self.W2, self.b2
 
     def _pre(self, x, u):
         """z = W1 [x;u] + b1"""
         return torch.cat((x, u), dim=-1) @ self.W1.to(x).t() + self.b1.to(x)
 
-    def _hidden(self, x, u):
-        return _ACT_FN[self.activation][0](self._pre(x, u))
+    def _step(self, x, u):
+        """(next state, pre-activations of every hidden layer)"""
+        act = _ACT_FN[self.activation][0]
+        zs = (self._pre(x, u),)
+        if self.depth == 2:
+            zs = zs + (act(zs[0]) @ self.W2.to(x).t() + self.b2.to(x),)
+        return self._output(act(zs[-1]), x), zs
 
     def _output(self, a, x):
-        nxt = a @ self.W2.to(x).t() + self.b2.to(x)
+        """the last layer on the last hidden layer's activations"""
+        W, b = self._weights()[-2:]
+        nxt = a @ W.to(x).t() + b.to(x)
         return nxt + x if self.residual else nxt
 
     def forward(self, x, u):
         """x [B,nx] (or [nx]), u [B,nu] (or [nu]) -> next state"""
         assert x.shape[-1] == self.n_state and u.shape[-1] == self.n_ctrl and x.shape[:-1] == u.shape[:-1]
-        return self._output(self._hidden(x, u), x)
+        return self._step(x, u)[0]
 
-    def _jacobian(self, z):
-        """d next / d [x;u] at the pre-activations z [B,H] -> [B,nx,ns], a constant of the graph"""
-        z = z.detach()
-        F = torch.einsum("ih,bh,hj->bij", self.W2.detach().to(z), _ACT_FN[self.activation][1](z), self.W1.detach().to(z))
+    def _jacobian(self, *zs):
+        """d next / d [x;u] at the pre-activations z [B,H] of every hidden layer -> [B,nx,ns], a constant of the graph:
+        W2 diag(act'(z)) W1, or W3 diag(act'(z2)) W2 diag(act'(z1)) W1, plus [I|0] when residual"""
+        dact = _ACT_FN[self.activation][1]
+        zs = [z.detach() for z in zs]
+        z = zs[0]
+        if self.depth == 2:
+            F = torch.einsum("ik,bk,kh,bh,hj->bij", self.W3.detach().to(z), dact(zs[1]), self.W2.detach().to(z), dact(z),
+                             self.W1.detach().to(z))
+        else:
+            F = torch.einsum("ih,bh,hj->bij", self.W2.detach().to(z), dact(z), self.W1.detach().to(z))
         if self.residual:
             F = F + torch.eye(self.n_state, self.n_state + self.n_ctrl, dtype=z.dtype, device=z.device)
         return F
@@ -145,7 +198,7 @@ class MlpDx(torch.nn.Module):
     def supported(self):
         """the kernels serve this size (asked of the library once; nothing is launched)"""
         if self._size_ok is None:
-            self._size_ok = bool(_lib.load().dmpc_mlp_dx_supported(self.n_state, self.n_ctrl, self.n_hidden, self.act_code))
+            self._size_ok = bool(_lib.load().dmpc_mlp_dx_supported(self.n_state, self.n_ctrl, self.hidden_code, self.act_code))
         return self._size_ok
 
     def _on_device(self, x_init, u):
@@ -161,17 +214,29 @@ class MlpDx(torch.nn.Module):
         return self._on_device(x_init, u) and not self._grad_wanted(x_init, u)
 
     def device_weights(self, device):
-        """(W1, b1, W2, b2) as the kernels take them - contiguous float32 on `device`; made on every call, never kept"""
-        return tuple(_lib.f32c(p.detach(), device) for p in self._weights())
+        """(W1, b1, W2, b2) as the kernels take them - contiguous float32 on `device`; made on every call, never kept.  Two
+        hidden layers: the last two are "the layers behind the first, one after the other", [W2 | W3] and [b2 | b3], one
+        `torch.cat` each."""
+        w = [_lib.f32c(p.detach(), device) for p in self._weights()]
+        if self.depth == 2:
+            return w[0], w[1], torch.cat((w[2].reshape(-1), w[4].reshape(-1))), torch.cat((w[3], w[5]))
+        return tuple(w)
+
+    def _packed_order(self):
+        """the parameters in the order of `packed_weights`"""
+        if self.depth == 2:
+            return self.W1, self.b1, self.W2, self.W3, self.b2, self.b3
+        return self._weights()
 
     def packed_weights(self, device):
-        """[W1 | b1 | W2 | b2] as ONE flat float32 buffer on `device`, the `F` of `dmpc_box_ddp`'s dyn_kind 2.  The buffer is
+        """[W1 | b1 | W2 | b2] - with two hidden layers [W1 | b1 | W2 | W3 | b2 | b3], so that the tails behind b1 are what
+        `device_weights` passes - as ONE flat float32 buffer on `device`, the `F` of `dmpc_box_ddp`'s dyn_kind 2.  The buffer is
         kept per device and refilled in place by one launch on every call: its address is stable (a recorded hipGraph keeps
         reading it) and an optimiser step in place is seen by the next solve - call this before every launch or replay."""
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
-        parts = [p.detach().reshape(-1) for p in self._weights()]
+        parts = [p.detach().reshape(-1) for p in self._packed_order()]
         if any(p.dtype != torch.float32 or p.device != device for p in parts):
             parts = [p.to(device=device, dtype=torch.float32) for p in parts]
         buf = self._packed.get(device)
@@ -181,8 +246,9 @@ class MlpDx(torch.nn.Module):
         return buf
 
     def host_params(self):
-        """dyn_params of `dmpc_box_ddp`'s dyn_kind 2: (n_hidden, act, residual, search_linearizes) as floats"""
-        return (float(self.n_hidden), float(self.act_code), 1.0 if self.residual else 0.0,
+        """dyn_params of `dmpc_box_ddp`'s dyn_kind 2: (n_hidden, act, residual, search_linearizes) as floats, n_hidden the
+        code of `hidden_code` (exact in float32)"""
+        return (float(self.hidden_code), float(self.act_code), 1.0 if self.residual else 0.0,
                 1.0 if self.SEARCH_LINEARIZES else 0.0)
 
     def rollout_linearize(self, x_init, u, want_model=True):
@@ -203,7 +269,7 @@ class MlpDx(torch.nn.Module):
         F = torch.empty((max(T - 1, 0), B, nx, nx + nu), dtype=torch.float32, device=d) if want_model else None
         f = torch.empty((max(T - 1, 0), B, nx), dtype=torch.float32, device=d) if want_model else None
         with _lib.guard(d):
-            rc = lib.dmpc_mlp_rollout_linearize(T, B, nx, nu, self.n_hidden, self.act_code, int(self.residual), _lib.ptr(W1),
+            rc = lib.dmpc_mlp_rollout_linearize(T, B, nx, nu, self.hidden_code, self.act_code, int(self.residual), _lib.ptr(W1),
                                                 _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2), _lib.ptr(x0), _lib.ptr(ud),
                                                 _lib.ptr(x), _lib.ptr(F), _lib.ptr(f), _lib.stream_ptr(d))
         _lib.check(rc, "dmpc_mlp_rollout_linearize")
@@ -213,10 +279,9 @@ class MlpDx(torch.nn.Module):
         T = u.shape[0]
         xs, Fs, fs = [x_init], [], []
         for t in range(T - 1):
-            z = self._pre(xs[t], u[t])
-            nxt = self._output(_ACT_FN[self.activation][0](z), xs[t])
+            nxt, zs = self._step(xs[t], u[t])
             if want_model:
-                Fs.append(self._jacobian(z))
+                Fs.append(self._jacobian(*zs))
                 fs.append(nxt - bmv(Fs[t], torch.cat((xs[t], u[t]), dim=1)))
             xs.append(nxt)
         x = torch.stack(xs, 0)
@@ -239,7 +304,7 @@ class MlpDx(torch.nn.Module):
         if not self._grad_wanted(x0, u):
             _, F, f = self._rollout_linearize_torch(x0, u, True)
             return F, f
-        if self.device_grad and self._on_device(x0, u):
+        if self.device_grad and self.depth == 1 and self._on_device(x0, u):
             return _DeviceLinearize.apply(self, *self._weights(), x0, u)
         F_dev = None
         if self._on_device(x0, u):
@@ -247,9 +312,8 @@ class MlpDx(torch.nn.Module):
         xs, Fs, fs = [x0], [], []
         for t in range(T - 1):
             xt, ut = xs[t], u[t]
-            z = self._pre(xt, ut)
-            nxt = self._output(_ACT_FN[self.activation][0](z), xt)
-            Ft = F_dev[t] if F_dev is not None else self._jacobian(z)
+            nxt, zs = self._step(xt, ut)
+            Ft = F_dev[t] if F_dev is not None else self._jacobian(*zs)
             Fs.append(Ft)
             fs.append(nxt - bmv(Ft, torch.cat((xt, ut), dim=1)))
             xs.append(nxt)
@@ -278,7 +342,7 @@ class _DeviceLinearize(torch.autograd.Function):
         m = ctx.model
         *weights, x, u = ctx.saved_tensors
         T, B = u.shape[0], u.shape[1]
-        nx, nu, H = m.n_state, m.n_ctrl, m.n_hidden
+        nx, nu, H = m.n_state, m.n_ctrl, m.hidden[0]
         lib = _lib.load()
         d = u.device
         W1, b1, W2, b2 = (_lib.f32c(p.detach(), d) for p in weights)

@@ -354,10 +354,10 @@ class MPCstep:
             g_, m_, l_ = (float(v) for v in true_dynamics.params.detach().cpu().tolist())
             entry, head = "dmpc_mpc_forward_rec_pendulum", (T, B)
             dyn = (g_, m_, l_, float(true_dynamics.dt), float(true_dynamics.max_torque))
-        elif quad and _is_device_mlp(true_dynamics, nx, nu):     # a learned one-hidden-layer network, weights as device pointers
+        elif quad and _is_device_mlp(true_dynamics, nx, nu):     # a learned network (one or two hidden layers), weights as device pointers
             W1, b1, W2, b2 = true_dynamics.device_weights(d)
             entry, dyn = "dmpc_mpc_forward_rec_mlp", ()
-            head = (T, B, nx, nu, true_dynamics.n_hidden, true_dynamics.act_code, int(true_dynamics.residual),
+            head = (T, B, nx, nu, true_dynamics.hidden_code, true_dynamics.act_code, int(true_dynamics.residual),
                     p(W1), p(b1), p(W2), p(b2))
         else:
             entry = None

@@ -298,31 +298,42 @@ int dmpc_pendulum_rollout_linearize(int T, int B, const float *x_init, const flo
                                     float dt, float max_torque, int clamp_grad_closed, float *x_out, float *F_out,
                                     float *f_out, dmpc_stream_t stream);
 
-/* A learned one-hidden-layer dynamics model (MlpDx of the Python layer) as the true dynamics:
- *     next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual != 0)
- * W1 [n_hidden,ns], b1 [n_hidden], W2 [nx,n_hidden], b2 [nx] are DEVICE arrays read by every launch - nothing is cached,
- * an optimiser step in place is seen by the next call.  `act` is a plain int; with z = W1 [x;u] + b1, a = act(z), d = act'(z):
+/* A learned dynamics model with one or two hidden layers (MlpDx of the Python layer) as the true dynamics:
+ *     one hidden layer:   next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual != 0)
+ *     two hidden layers:  z1 = W1 [x;u] + b1, a1 = act(z1);  z2 = W2 a1 + b2, a2 = act(z2);  next = W3 a2 + b3 (+ x)
+ * `n_hidden` is H1 | (H2 << 16), DMPC_MLP_HIDDEN2(H1, H2).  H2 = 0 - a plain integer - is one hidden layer of H1 units.
+ * H2 >= 1 is two hidden layers of H1 and H2 units with the same activation.
+ * W1 [H1,ns], b1 [H1] and "the layers behind the first, one after the other" are DEVICE arrays of contiguous float32 read by
+ * every launch - nothing is cached, an optimiser step in place is seen by the next call:
+ *     one hidden layer:   W2 [nx,H1],                        b2 [nx]
+ *     two hidden layers:  W2 = [W2 (H2*H1) | W3 (nx*H2)],    b2 = [b2 (H2) | b3 (nx)]
+ * `act` is a plain int; with z a pre-activation, a = act(z), d = act'(z):
  *     0  tanh      a = tanh(z)                          d = 1 - a^2
  *     1  never assigned: DMPC_E_UNSUPPORTED, for good
  *     2  relu      a = z > 0 ? z : 0 (NaN for a NaN z)  d = z > 0 ? 1 : 0   (0 at z = 0, torch's convention)
  *     3  silu      a = z s,  s = 1 / (1 + exp(-z))      d = s (1 + z (1 - s))
  *     4  softplus  a = max(z, 0) + log1p(exp(-|z|))     d = 1 / (1 + exp(-z))
  * (torch.nn.Softplus at its defaults beta = 1, threshold = 20: beyond the threshold the two differ by less than 2.1e-9,
- * below float32's resolution there.)  Any other value, negative ones included: DMPC_E_UNSUPPORTED.  The activation selects
- * a kernel instance at compile time; the tanh instances compute what they computed before the others existed.  Sizes: nx <= 16, nu <= 8, 1 <= n_hidden <= 256, else DMPC_E_UNSUPPORTED (a NULL pointer or a
+ * below float32's resolution there.)  Any other value, negative ones included: DMPC_E_UNSUPPORTED.  The activation and the
+ * depth select a kernel instance at compile time; the one-layer instances compute what they computed before the second depth
+ * existed.  Sizes: nx <= 16, nu <= 8, and 1 <= H1 <= 256 with one hidden layer, 1 <= H1 <= 128 and 1 <= H2 <= 128 with two,
+ * else DMPC_E_UNSUPPORTED (a NULL pointer or a
  * non-positive T, B, nx, nu: DMPC_E_BADARG; both before any HIP call, dmpc_mlp_dx_supported launches nothing); also
- * DMPC_E_UNSUPPORTED where an output array would reach 2^31 elements.  One wavefront per trajectory, the weights in LDS,
- * and ONE step function per activation for both entry points: the states of dmpc_mlp_rollout_linearize and the
+ * DMPC_E_UNSUPPORTED where an output array would reach 2^31 elements.  One wavefront per trajectory, the weights in LDS
+ * (up to 88 KB, with the Jacobian's scratch 132 KB, at the two-layer limits: one workgroup per CU),
+ * and ONE step function per activation and depth for both entry points: the states of dmpc_mlp_rollout_linearize and the
  * candidates of the search are bit-equal for equal controls, whatever B is.
  *
  * dmpc_mlp_rollout_linearize: get_traj (util.py:239-277) and linearize_dynamics (mpc/approximate.py:77-119, there by
- *   chainer.grad) in one launch: x_0 = x_init, x_{t+1} = next(x_t, u_t), F_t = [I|0] residual + W2 diag(d_t) W1,
+ *   chainer.grad) in one launch: x_0 = x_init, x_{t+1} = next(x_t, u_t), F_t = [I|0] residual + W2 diag(d_t) W1
+ *   (two hidden layers: + W3 diag(d2_t) W2 diag(d1_t) W1),
  *   f_t = x_{t+1} - F_t [x_t;u_t].  x_out [T,B,nx]; F_out [T-1,B,nx,ns] or NULL; f_out [T-1,B,nx] or NULL (NULL with F_out
  *   NULL).  T = 1: x_out = x_init, nothing else is written.
  * dmpc_mpc_forward_rec_mlp: dmpc_mpc_forward_rec (its arguments, outputs, per-trajectory termination, bound snap, test on the
  *   cost difference, cap of 64 passes with DMPC_INFO_LS_ITERCAP, DMPC_INFO_NONFINITE) with the network in place of
  *   F_true, f_true.
- * dmpc_mlp_param_grad: the gradient of a loss L(f) of dmpc_mlp_rollout_linearize's f with respect to the weights, F_t held
+ * dmpc_mlp_param_grad (one hidden layer only: a two-layer `n_hidden` is DMPC_E_UNSUPPORTED, its workspace query 0 - that
+ *   gradient is taken by autograd through a live rollout): the gradient of a loss L(f) of dmpc_mlp_rollout_linearize's f with respect to the weights, F_t held
  *   constant at the value of the live Jacobian (mpc/approximate.py:77-119).  x [T,B,nx] are the states that launch stored,
  *   grad_f [T-1,B,nx] = dL/df (may be NULL when T = 1).  dW1 [n_hidden,ns], db1 [n_hidden], dW2 [nx,n_hidden], db2 [nx] are
  *   WRITTEN (not added to): sum over t and b of r a_t^T, r, delta z_t^T, delta with r = grad_f_t and
@@ -333,6 +344,7 @@ int dmpc_pendulum_rollout_linearize(int T, int B, const float *x_init, const flo
  *   from call to call and depends on (T, B, nx, nu, n_hidden) and the data alone.  ws: device memory of at least
  *   dmpc_mlp_param_grad_workspace_bytes (0 for a size the kernels refuse), else DMPC_E_WORKSPACE; not needed when T = 1,
  *   which only zeroes the outputs.  No allocation, no host synchronisation. */
+#define DMPC_MLP_HIDDEN2(h1, h2) ((int)(h1) | ((int)(h2) << 16))
 int dmpc_mlp_dx_supported(int nx, int nu, int n_hidden, int act);
 int dmpc_mlp_rollout_linearize(int T, int B, int nx, int nu, int n_hidden, int act, int residual, const float *W1,
                                const float *b1, const float *W2, const float *b2, const float *x_init, const float *u,
@@ -378,9 +390,11 @@ int dmpc_lin_rollout(int T, int B, int nx, int nu, const float *x_init, const fl
  *   DMPC_NO_DDP_ITER_FUSED=1: 22-23, bit-identical.  The chain contains no host synchronisation and no allocation: it can be
  *   recorded in a hipGraph (batch_coupled = 0) - BoxDDP (box_ddp.py) does so by itself for a solve called again on the same buffers.
  * dyn_kind 2: the learned model of the MlpDx section above as the true dynamics.  F is ONE device array of contiguous
- *   float32, 16-byte aligned, holding the packed weights [W1 (n_hidden*ns) | b1 (n_hidden) | W2 (nx*n_hidden) | b2 (nx)],
+ *   float32, 16-byte aligned, holding the packed weights [W1 (H1*ns) | b1 (H1) | W2 (nx*H1) | b2 (nx)] - with two hidden
+ *   layers [W1 (H1*ns) | b1 (H1) | W2 (H2*H1) | W3 (nx*H2) | b2 (H2) | b3 (nx)] -
  *   each laid out as dmpc_mlp_rollout_linearize takes it and read by every launch (nothing is cached); f must be NULL;
- *   dyn_params = HOST array {n_hidden, act, residual, search_linearizes}: `act` the code of the MlpDx section, the last two
+ *   dyn_params = HOST array {n_hidden, act, residual, search_linearizes}: n_hidden the code of the MlpDx section as an
+ *   integral float (DMPC_MLP_HIDDEN2(128, 128) is exact in float32), `act` that section's code, the last two
  *   0 or 1.  F or dyn_params NULL, f not NULL, a negative or non-integral n_hidden / act, a flag other than 0 or 1:
  *   DMPC_E_BADARG.  A size or activation dmpc_mlp_dx_supported refuses, or batch_coupled != 0: DMPC_E_UNSUPPORTED - as is
  *   every dyn_kind below 0 or above 2.  All of it before the first HIP call; the workspace is dmpc_box_ddp_workspace_bytes'.

@@ -200,6 +200,29 @@ int main() {
                      DMPC_E_WORKSPACE);
             }
           }
+  // two hidden layers: n_hidden = DMPC_MLP_HIDDEN2(H1, H2); the rollout and the search take it, the weight gradient refuses it
+  for (int H1 : {0, 1, 5, 128, 129})
+    for (int H2 : {1, 7, 128, 129})
+      for (int T : {1, 2, 20}) {
+        const int H = DMPC_MLP_HIDDEN2(H1, H2);
+        const bool ok = H1 >= 1 && H1 <= 128 && H2 <= 128;
+        EXPECT(dmpc_mlp_dx_supported(16, 8, H, 3) == (ok ? 1 : 0));
+        const int rr = dmpc_mlp_rollout_linearize(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, nullptr);
+        const int rs = dmpc_mpc_forward_rec_mlp(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, p, p, p, 0.2f, 10, p, p, p, p, p, p,
+                                                p, pi, pi, nullptr);
+        if (!ok) EXPECT(rr == DMPC_E_UNSUPPORTED && (T == 1 ? rs == DMPC_E_BADARG : rs == DMPC_E_UNSUPPORTED));
+        else EXPECT(rr >= 0 && (T == 1 ? rs == DMPC_E_BADARG : rs >= 0));
+        EXPECT(dmpc_mlp_rollout_linearize(T, 5, 16, 8, H, 3, 1, p, p, nullptr, p, p, p, p, p, p, nullptr) == DMPC_E_BADARG);
+        EXPECT(dmpc_mlp_param_grad_workspace_bytes(5, 16, 8, H) == 0);
+        EXPECT(dmpc_mlp_param_grad(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, ws, 1 << 20, nullptr) ==
+               DMPC_E_UNSUPPORTED);
+        const float mlp2[4] = {(float)H, 3.f, 1.f, 0.f};
+        if (T > 1) {
+          const int rm = dmpc_box_ddp(T, 4, 16, 8, p, p, p, p, nullptr, 2, mlp2, p, p, p, 1e-3f, 5, 0.2f, 10, 1e-3f, 3, 20, 0, 0, p, p, p,
+                                      p, p, pi, ws, dmpc_box_ddp_workspace_bytes(T, 4, 16, 8), nullptr, nullptr);
+          EXPECT(ok ? rm >= 0 : rm == DMPC_E_UNSUPPORTED);
+        }
+      }
   EXPECT(dmpc_mlp_param_grad_partials(0) == 0 && dmpc_mlp_param_grad_partials(1 << 30) == dmpc_mlp_param_grad_partials(1 << 20));
   EXPECT(dmpc_lqr_shared_workspace_bytes(0, 1, 1, 1) == 0 && dmpc_lqr_shared_saved_bytes(0, 1, 1) == 0);
   EXPECT(dmpc_lqr_kernel_family(0, 3) == DMPC_E_UNSUPPORTED);

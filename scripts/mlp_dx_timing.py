@@ -1,4 +1,4 @@
-"""One `BoxDDP` solve under a learned one-hidden-layer dynamics model, two ways in the same run:
+"""One `BoxDDP` solve under a learned dynamics model with one or two hidden layers, two ways in the same run:
   device   - the `MlpDx` module itself: rollout + linearisation in one launch, the line search inside its kernel;
   callable - the same module behind `lambda x, u: m(x, u)`: `linearize_dynamics` through torch.autograd and the line search
              as torch ops around the callable - the route every non-linear dynamics took before `MlpDx` (the baseline).
@@ -15,8 +15,11 @@ chain with the network inside it (`device_loop=True`: `search_linearizes` 0 and 
 `--activation` picks the network (tanh, relu, silu, softplus; default tanh, whose output lines are what they were before
 the flag existed - another activation adds an "activation" key).
 
+`--hidden2 H2` makes every case a two-layer network: the H of `--cases` is its first width, H2 its second ("n_hidden" is then
+the pair).  The run fails if the device route is not faster than the plain callable measured beside it.
+
     python scripts/mlp_dx_timing.py [--grad | --chain] [--iters 20] [--warmup 3] [--cases 3x1x32,8x2x64] [--batch 128] [--horizon 20]
-                                    [--activation tanh] [--json out]"""
+                                    [--activation tanh] [--hidden2 H2] [--json out]"""
 import argparse
 import json
 import os
@@ -184,14 +187,19 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--horizon", type=int, default=20)
     ap.add_argument("--activation", default="tanh", choices=["tanh", "relu", "silu", "softplus"])
+    ap.add_argument("--hidden2", type=int, default=0)
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     res = []
     for c in a.cases.split(","):
         nx, nu, H = (int(v) for v in c.split("x"))
+        if a.hidden2 > 0:
+            H = (H, a.hidden2)
         r = (run_chain_case if a.chain else run_grad_case if a.grad else run_case)(nx, nu, H, a.batch, a.horizon, max(a.iters, 20), a.warmup, a.activation)
         print(json.dumps(r), flush=True)
         res.append(r)
+        if a.hidden2 > 0 and not (a.chain or a.grad):
+            assert r["device_ms"] < r["callable_ms"], "the device route is not faster than the plain callable"
     if a.json:
         with open(a.json, "w") as fh:
             json.dump(res, fh, indent=1)
