@@ -19,7 +19,7 @@ static int mlp_check(int nx, int nu, int n_hidden, int act) {
   if (act != kMlpActTanh && act != kMlpActRelu && act != kMlpActSilu && act != kMlpActSoftplus) return DMPC_E_UNSUPPORTED;
   if (nx > kMlpMaxNx || nu > kMlpMaxNu || n_hidden < 1) return DMPC_E_UNSUPPORTED;
   const int H1 = mlp_hidden1(n_hidden), H2 = mlp_hidden2(n_hidden);
-  if (H2 == 0 ? H1 > kMlpMaxHidden : (H1 < 1 || H1 > kMlp2MaxHidden || H2 > kMlp2MaxHidden)) return DMPC_E_UNSUPPORTED;
+  if (H2 == 0 ? H1 > mlp_max_hidden(1) : (H1 < 1 || H1 > mlp_max_hidden(2) || H2 > mlp_max_hidden(2))) return DMPC_E_UNSUPPORTED;
   if (mlp_lds_bytes(nx, nu, H1, H2) > kMlpLdsLimit) return DMPC_E_UNSUPPORTED;
   return 0;
 }
@@ -44,21 +44,21 @@ static void mlp_launch(K kernel, int B, size_t bytes, hipStream_t stream, const 
 
 // the two launchers of mlp_dx_launch.hpp: the entry points below and dmpc_box_ddp's chain (mpc_api.hip) go through them
 void launch_mlp_rollout(const MlpRolloutArgs &a, int act, hipStream_t stream) {
-  const size_t bytes = mlp_lds_bytes(a.m.nx, a.m.nu, a.m.n_hidden, a.m.n_hidden2, a.F != nullptr);
+  const size_t bytes = mlp_lds_bytes(a.m.nx, a.m.nu, a.m.H[0], a.m.H[1], a.F != nullptr);
   mlp_with_act(act, [&](auto A) {
     constexpr int ACT = decltype(A)::value;
     void (*kernel)(const MlpRolloutArgs) =
-        a.m.n_hidden2 > 0 ? &mlp_rollout_linearize_kernel<ACT, 2> : &mlp_rollout_linearize_kernel<ACT>;
+        a.m.depth == 2 ? &mlp_rollout_linearize_kernel<ACT, 2> : &mlp_rollout_linearize_kernel<ACT>;
     mlp_launch(kernel, a.B, bytes, stream, a);
   });
 }
 
 void launch_mlp_search(const MpcFwdArgs &a, const MlpModel &m, int act, hipStream_t stream) {
-  const size_t bytes = mlp_lds_bytes(m.nx, m.nu, m.n_hidden, m.n_hidden2, a.F_next != nullptr);
+  const size_t bytes = mlp_lds_bytes(m.nx, m.nu, m.H[0], m.H[1], a.F_next != nullptr);
   mlp_with_act(act, [&](auto A) {
     constexpr int ACT = decltype(A)::value;
     void (*kernel)(const MpcFwdArgs, const MlpModel) =
-        m.n_hidden2 > 0 ? &mpc_forward_rec_mlp_kernel<ACT, 2> : &mpc_forward_rec_mlp_kernel<ACT>;
+        m.depth == 2 ? &mpc_forward_rec_mlp_kernel<ACT, 2> : &mpc_forward_rec_mlp_kernel<ACT>;
     mlp_launch(kernel, a.B, bytes, stream, a, m);
   });
 }
@@ -132,8 +132,7 @@ int dmpc_mlp_param_grad(int T, int B, int nx, int nu, int n_hidden, int act, int
     if (e == hipSuccess && d_u != nullptr) e = hipMemsetAsync(d_u, 0, (size_t)B * nu * sizeof(float), stream);
     if (e != hipSuccess) return (int)e;
   } else {
-    MlpGradArgs ga{T, B, G, MlpModel{nx, nu, n_hidden, residual != 0 ? 1 : 0, W1, b1, W2, b2}, x, u, grad_f,
-                   static_cast<float *>(ws), d_x_init, d_u};
+    MlpGradArgs ga{T, B, G, mlp_model(nx, nu, n_hidden, residual, W1, b1, W2, b2), x, u, grad_f, static_cast<float *>(ws), d_x_init, d_u};
     mlp_with_act(act, [&](auto A) {
       DMPC_LAUNCH_GGL(mlp_param_grad_kernel<decltype(A)::value>, dim3((G + kMlpWaves - 1) / kMlpWaves),
                       dim3(64 * kMlpWaves), mlp_lds_bytes(nx, nu, n_hidden), stream, ga);

@@ -1,39 +1,46 @@
-// mlp_dx_kernels.hpp - a learned dynamics model with one or two hidden layers on the device (MlpDx of the Python layer):
+// mlp_dx_kernels.hpp - a learned dynamics model with DEPTH = 1 or 2 hidden layers on the device (MlpDx of the Python layer):
 //
-//     depth 1:  next(x, u) = W2 act(W1 [x;u] + b1) + b2 (+ x when residual),     act = tanh | relu | silu | softplus
-//     depth 2:  next(x, u) = W3 act(W2 act(W1 [x;u] + b1) + b2) + b3 (+ x when residual)
+//     a_0 = [x;u],   z_l = W_l a_{l-1} + b_l,  a_l = act(z_l)   for the hidden layers l = 1 .. DEPTH,
+//     next(x, u) = W_{DEPTH+1} a_DEPTH + b_{DEPTH+1} (+ x when residual),        act = tanh | relu | silu | softplus
 //
-// The activation is a template parameter of the three kernels that evaluate the network (mlp_act below is the only place
-// where it is looked at): a = act(z) and d = act'(z) of the pre-activation z = W1 [x;u] + b1.  The depth is a second
-// template parameter of the rollout and the search (MlpNet<DEPTH> below); the depth-one instances run the functions they
-// ran before the second depth existed.  The two-layer network is described behind the one-layer functions ("Depth two").
+// The network is written ONCE, by layers, each piece templated on the hidden units a lane owns (UNITS: 4 at depth one, H <= 256;
+// 2 at depth two, H1, H2 <= 128 - the register arrays have that size, so the two depths do not share a value of it):
+//     MlpUnits                 which units of a layer this lane owns (lane, lane + 64, ...), clamped addresses, the live mask
+//     mlp_layer_from_lanes     a hidden layer whose inputs sit one per lane: layer 1
+//     mlp_layer_from_units     a hidden layer whose inputs are the previous layer's units in registers: layer 2 (and a third)
+//     mlp_activate             mlp_act<ACT> on one of a lane's units under the live mask: a = act(z), d = act'(z), zeros beyond the width
+//     mlp_output_layer         one butterfly reduction per output, bias, residual
+//     mlp_fold_output          N = W3 D2 W2: the output layer folded through layer 2 (depth two's Jacobian only)
+//     mlp_jacobian_tail        F = left D1 W1 + [I|0], its stores, f = next - F tau;  left = W2 at depth one, N at depth two
+// MlpNet<DEPTH> composes them into `next` and `jacobian_store`; the activation and the depth are template parameters of the
+// kernels, and mlp_act is the only place where the activation is looked at.
 //
 //   mlp_rollout_linearize_kernel   get_traj + linearize_dynamics (util.py:239-277, mpc/approximate.py:77-119) in one
-//                                  launch: x_{t+1} = next(x_t, u_t), F_t = [I|0] residual + W2 diag(d) W1,
-//                                  f_t = next - F_t [x_t;u_t].
+//                                  launch: x_{t+1} = next(x_t, u_t), F_t = d next / d [x;u], f_t = next - F_t [x_t;u_t].
 //   mpc_forward_rec_mlp_kernel     MPCstep.forward_rec (mpc/mpc_step.py:175-286) with the network as the TRUE dynamics:
 //                                  the clamped closed-loop rollout and per-trajectory line search of
 //                                  mpc_generic_forward_kernel, the dynamics evaluated in place of F tau + f.
-//   mlp_param_grad_kernel,         the gradient of a loss of the rollout's f with respect to W1, b1, W2, b2: per-wavefront
+//   mlp_param_grad_kernel,         the gradient of a loss of the rollout's f with respect to W1, b1, W2, b2 (depth one): per-wavefront
 //   mlp_param_grad_reduce_kernel   sums in registers, then a fixed-order reduction of the partials (at the end of this file).
 //
-// Layout.  Runtime dimensions (nx <= 16, nu <= 8, 1 <= H <= 256), ONE wavefront per trajectory, four per workgroup.
-// The weights are staged into LDS once per workgroup and shared by its wavefronts:
-//     W1s [H][ns | 1]   lane l owns hidden units l, l + 64, ...: it walks ITS row, and the odd stride puts the 64 rows a
-//                       wavefront reads at once on 64 different banks
-//     W2s [nx][H | 1]   lanes read consecutive units of a row (no conflict); the odd stride separates the rows that the
-//                       Jacobian's lanes read at once
-//     b1s [H], b2s [nx]
-// 25.6 + 16.4 + 1.1 KB at the largest size.  Behind them every wavefront has 672 floats of its own (d per hidden
-// unit, the step's Jacobian).  Element i of tau = [x;u] lives in lane i; a value another lane needs is read from that
-// lane's register (v_readlane), never through LDS, so the search needs no barrier after the staging one and its
-// wavefronts leave the loop one by one.
+// Layout.  Runtime dimensions (nx <= 16, nu <= 8), ONE wavefront per trajectory, four per workgroup.  The weights are
+// staged into LDS once per workgroup (mlp_stage) and shared by its wavefronts - the matrices in layer order, then the biases:
+//     W[l] [out_l][in_l | 1]   a hidden layer: lane l owns units l, l + 64, ...: it walks ITS row, and the odd stride puts the 64
+//                              rows a wavefront reads at once on 64 different banks.  The output layer: lanes read consecutive
+//                              units of a row (no conflict); the odd stride separates the rows the Jacobian's lanes read at once
+//     b[l] [out_l]
+// 43.1 KB at depth one's largest size, 88.2 KB at depth two's (nx 16, nu 8, H1 = H2 = 128).  Behind them every wavefront has a
+// slice of its own (mlp_wave_floats: d per hidden unit, depth two's N, the step's Jacobian): 672 floats at depth one, which
+// every depth-one launch carries; 2,704 at depth two, only in a launch that forms Jacobians - 131.5 KB then, one workgroup per
+// CU.  Element i of tau = [x;u] lives in lane i; a value another lane needs - an element of tau, a layer-1 activation - is read
+// from that lane's register (v_readlane), never through LDS, so the step function touches no slice, the search needs no
+// barrier after the staging one and its wavefronts leave the loop one by one.
 //
 // Bit-equal dynamics.  The search ends when a candidate collapses onto the nominal trajectory and its cost difference is
-// exactly 0 (see PendulumModel in mpc_kernels.hpp).  Both kernels evaluate the network through mlp_next alone: explicit
-// fmaf, inputs in ascending order, a lane's hidden units in ascending order, one butterfly reduction per output - an
-// order that depends on (nx, nu, H) and the activation and on nothing else: not on B, the grid, or the wavefront's slot in
-// its workgroup.
+// exactly 0 (see PendulumModel in mpc_kernels.hpp).  Every kernel evaluates the network through the pieces above alone:
+// explicit fmaf, a layer's inputs in ascending order, a lane's units in ascending order, one butterfly reduction per output;
+// units beyond a width hold exact zeros and read clamped addresses - an order that depends on (nx, nu, the widths) and the
+// activation and on nothing else: not on B, the grid, or the wavefront's slot in its workgroup.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,34 +55,28 @@
 
 namespace dmpc {
 
-constexpr int kMlpMaxNx = 16, kMlpMaxNu = 8, kMlpMaxHidden = 256;
+constexpr int kMlpMaxNx = 16, kMlpMaxNu = 8;
 constexpr int kMlpWaves = 4;                                 // trajectories (wavefronts) per workgroup
-constexpr int kMlpUnits = kMlpMaxHidden / 64;                // hidden units per lane, at most
-constexpr int kMlpWaveFloats = kMlpMaxHidden + kMlpMaxNx * (kMlpMaxNx + kMlpMaxNu) + 32;
-
-struct MlpLds {
-  int nsp, hp;                      // row strides of W1s and W2s
-  float *W1s, *W2s, *b1s, *b2s, *wave;
-};
-__host__ __device__ inline int mlp_lds_floats(int nx, int nu, int H) {
-  return H * ((nx + nu) | 1) + nx * (H | 1) + H + nx;
-}
-
-// depth two: H1, H2 <= 128, so a lane owns at most two units of either layer
-constexpr int kMlp2MaxHidden = 128;
-constexpr int kMlp2Units = kMlp2MaxHidden / 64;
-// a wavefront's own floats: d1 and d2 per hidden unit, N = W3 D2 W2 with an odd row stride, the step's Jacobian
-constexpr int kMlp2WaveFloats = 2 * kMlp2MaxHidden + kMlpMaxNx * (kMlp2MaxHidden | 1) + kMlpMaxNx * (kMlpMaxNx + kMlpMaxNu);
-__host__ __device__ inline int mlp2_lds_floats(int nx, int nu, int H1, int H2) {
-  return H1 * ((nx + nu) | 1) + H2 * (H1 | 1) + nx * (H2 | 1) + H1 + H2 + nx;
+constexpr int mlp_max_hidden(int depth) { return depth == 1 ? 256 : 128; }
+constexpr int mlp_units(int depth) { return mlp_max_hidden(depth) / 64; }      // hidden units per lane, at most
+// a wavefront's own floats: d per hidden unit and layer; depth two: N with an odd row stride (depth one: 32 floats its
+// launches have always carried); the step's Jacobian
+constexpr int mlp_wave_floats(int depth) {
+  return depth * mlp_max_hidden(depth) + (depth == 1 ? 32 : kMlpMaxNx * (mlp_max_hidden(depth) | 1)) + kMlpMaxNx * (kMlpMaxNx + kMlpMaxNu);
 }
 
 // THE byte count of a launch's dynamic LDS, for the launchers and for dmpc_mlp_dx_supported.  H2 = 0: one hidden layer.
 // `jacobian`: the launch forms F (depth one always has its slices: its instances are what they were).
-inline size_t mlp_lds_bytes(int nx, int nu, int H1, int H2 = 0, bool jacobian = true) {
-  if (H2 == 0) return (size_t)(mlp_lds_floats(nx, nu, H1) + kMlpWaves * kMlpWaveFloats) * sizeof(float);
-  return (size_t)(mlp2_lds_floats(nx, nu, H1, H2) + (jacobian ? kMlpWaves * kMlp2WaveFloats : 0)) * sizeof(float);
+constexpr size_t mlp_lds_bytes(int nx, int nu, int H1, int H2 = 0, bool jacobian = true) {
+  const int depth = H2 > 0 ? 2 : 1, last = H2 > 0 ? H2 : H1;
+  int floats = H1 * ((nx + nu) | 1) + H1 + nx * (last | 1) + nx;
+  if (depth == 2) floats += H2 * (H1 | 1) + H2;
+  if (depth == 1 || jacobian) floats += kMlpWaves * mlp_wave_floats(depth);
+  return (size_t)floats * sizeof(float);
 }
+static_assert(mlp_lds_bytes(16, 8, 256) == 53888, "depth one at every limit");
+static_assert(mlp_lds_bytes(16, 8, 128, 128, false) == 88192, "depth two at every limit, no Jacobian slices");
+static_assert(mlp_lds_bytes(16, 8, 128, 128, true) == 131456, "depth two at every limit, with its Jacobian slices");
 constexpr size_t kMlpLdsLimit = 160 * 1024;   // a gfx950 CU's LDS: one workgroup of the largest two-layer model
 
 __device__ __forceinline__ float lane_value(float v, int l) {   // l is wave-uniform
@@ -107,101 +108,193 @@ __device__ __forceinline__ void mlp_act(const float z, float &a, float &d) {
   }
 }
 
-// every thread of the workgroup takes part, also those of wavefronts without a trajectory; ends with the one barrier
-__device__ __forceinline__ MlpLds mlp_stage(const MlpModel &m, float *lds) {
-  const int ns = m.nx + m.nu, H = m.n_hidden;
-  MlpLds L;
-  L.nsp = ns | 1;
-  L.hp = H | 1;
-  L.W1s = lds;
-  L.W2s = L.W1s + H * L.nsp;
-  L.b1s = L.W2s + m.nx * L.hp;
-  L.b2s = L.b1s + H;
-  L.wave = L.b2s + m.nx + (threadIdx.x / 64) * kMlpWaveFloats;
+// layer l of a DEPTH-layer model: its inputs and outputs (l and DEPTH are compile-time constants wherever this is called)
+__device__ __forceinline__ int mlp_in(const MlpModel &m, int l) { return l == 0 ? m.nx + m.nu : m.H[l - 1]; }
+__device__ __forceinline__ int mlp_out(const MlpModel &m, int l, int depth) { return l < depth ? m.H[l] : m.nx; }
+
+// The staged network: layer l's matrix with row stride ld[l] = in_l | 1 and its bias; `wave`: this wavefront's slice (only a
+// launch that forms Jacobians, or a depth-one launch, has it).
+template <int DEPTH>
+struct MlpLds {
+  int ld[DEPTH + 1];
+  float *W[DEPTH + 1], *b[DEPTH + 1], *wave;
+};
+
+// one padded matrix and its bias into LDS, by every thread of the workgroup
+__device__ __forceinline__ void mlp_stage_layer(float *Ws, const int ld, float *bs, const float *W, const float *b, const int rows,
+                                                const int cols) {
   const int tid = threadIdx.x, nt = blockDim.x;
-  for (int e = tid; e < H * ns; e += nt) L.W1s[(e / ns) * L.nsp + (e % ns)] = m.W1[e];
-  for (int e = tid; e < m.nx * H; e += nt) L.W2s[(e / H) * L.hp + (e % H)] = m.W2[e];
-  for (int e = tid; e < H; e += nt) L.b1s[e] = m.b1[e];
-  for (int e = tid; e < m.nx; e += nt) L.b2s[e] = m.b2[e];
+  for (int e = tid; e < rows * cols; e += nt) Ws[(e / cols) * ld + (e % cols)] = W[e];
+  for (int e = tid; e < rows; e += nt) bs[e] = b[e];
+}
+
+// every thread of the workgroup takes part, also those of wavefronts without a trajectory; ends with the one barrier
+template <int DEPTH>
+__device__ __forceinline__ MlpLds<DEPTH> mlp_stage(const MlpModel &m, float *lds) {
+  MlpLds<DEPTH> L;
+  float *p = lds;
+#pragma unroll
+  for (int l = 0; l <= DEPTH; ++l) {
+    L.ld[l] = mlp_in(m, l) | 1;
+    L.W[l] = p;
+    p += mlp_out(m, l, DEPTH) * L.ld[l];
+  }
+#pragma unroll
+  for (int l = 0; l <= DEPTH; ++l) {
+    L.b[l] = p;
+    p += mlp_out(m, l, DEPTH);
+  }
+  L.wave = p + (threadIdx.x / 64) * mlp_wave_floats(DEPTH);
+#pragma unroll
+  for (int l = 0; l <= DEPTH; ++l) mlp_stage_layer(L.W[l], L.ld[l], L.b[l], m.layer[l].W, m.layer[l].b, mlp_out(m, l, DEPTH), mlp_in(m, l));
   __syncthreads();
   return L;
 }
 
-// ONE step of the model.  tau: element `lane` of [x;u] (anything in lanes >= ns: never read).  Returns element `lane` of the
-// next state (0 in lanes >= nx) and leaves this lane's activations in a[] and their derivatives in d[] - both 0 for units
-// beyond H, which therefore add exact zeros to every sum and whose LDS addresses are clamped into range.  A caller that
-// does not read d[] does not pay for it: everything here is inlined.
-template <int ACT>
-__device__ __forceinline__ float mlp_next(const MlpModel &m, const MlpLds &L, const int lane, const float tau,
-                                          float (&a)[kMlpUnits], float (&d)[kMlpUnits]) {
-  const int ns = m.nx + m.nu, H = m.n_hidden;
-  const int n_units = (H + 63) / 64;
-  int row[kMlpUnits];
-  bool has[kMlpUnits];
-  float z[kMlpUnits];
+// The units of a layer of width H that this lane owns: unit k is lane + 64 k.  Units beyond H hold exact zeros, add exact
+// zeros to every sum, and their LDS addresses are clamped into range (row[]); `n` is wave-uniform.
+template <int UNITS>
+struct MlpUnits {
+  int n, row[UNITS];
+  bool has[UNITS];
+  __device__ __forceinline__ MlpUnits(const int lane, const int H) : n((H + 63) / 64) {
 #pragma unroll
-  for (int k = 0; k < kMlpUnits; ++k) {
-    const int h = lane + 64 * k;
-    has[k] = h < H;
-    row[k] = has[k] ? h : H - 1;
-    z[k] = has[k] ? L.b1s[row[k]] : 0.f;
+    for (int k = 0; k < UNITS; ++k) {
+      const int h = lane + 64 * k;
+      has[k] = h < H;
+      row[k] = has[k] ? h : H - 1;
+    }
   }
-  for (int j = 0; j < ns; ++j) {
+  __device__ __forceinline__ bool live(const int k) const { return k < n && has[k]; }
+};
+
+template <int UNITS>
+__device__ __forceinline__ void mlp_bias(const float *bs, const MlpUnits<UNITS> &U, float (&z)[UNITS]) {
+#pragma unroll
+  for (int k = 0; k < UNITS; ++k) z[k] = U.has[k] ? bs[U.row[k]] : 0.f;
+}
+
+// z = W tau + b at this lane's units, element j of tau in lane j (anything in lanes >= n_in: never read); j ascending
+template <int UNITS>
+__device__ __forceinline__ void mlp_layer_from_lanes(const float *Ws, const int ld, const float *bs, const MlpUnits<UNITS> &U,
+                                                     const int n_in, const float tau, float (&z)[UNITS]) {
+  mlp_bias(bs, U, z);
+  for (int j = 0; j < n_in; ++j) {
     const float tj = lane_value(tau, j);
 #pragma unroll
-    for (int k = 0; k < kMlpUnits; ++k) {
-      if (k < n_units) {
-        const float w = L.W1s[row[k] * L.nsp + j];
-        z[k] = fmaf(has[k] ? w : 0.f, tj, z[k]);
+    for (int k = 0; k < UNITS; ++k) {
+      if (k < U.n) {
+        const float w = Ws[U.row[k] * ld + j];
+        z[k] = fmaf(U.has[k] ? w : 0.f, tj, z[k]);
       }
     }
   }
+}
+
+// z = W a_in + b at this lane's units, unit h = 64 k1 + l of the n_in inputs in a_in[k1] of lane l; h ascending
+template <int UNITS_IN, int UNITS_OUT>
+__device__ __forceinline__ void mlp_layer_from_units(const float *Ws, const int ld, const float *bs, const MlpUnits<UNITS_OUT> &U,
+                                                     const int n_in, const float (&a_in)[UNITS_IN], float (&z)[UNITS_OUT]) {
+  mlp_bias(bs, U, z);
 #pragma unroll
-  for (int k = 0; k < kMlpUnits; ++k) {
-    float ak, dk;
-    mlp_act<ACT>(z[k], ak, dk);
-    const bool live = k < n_units && has[k];
-    a[k] = live ? ak : 0.f;
-    d[k] = live ? dk : 0.f;
+  for (int k1 = 0; k1 < UNITS_IN; ++k1) {
+    const int left = n_in - 64 * k1, cnt = left < 64 ? left : 64;
+    for (int l = 0; l < cnt; ++l) {
+      const float ah = lane_value(a_in[k1], l);
+#pragma unroll
+      for (int k = 0; k < UNITS_OUT; ++k) {
+        if (k < U.n) {
+          const float w = Ws[U.row[k] * ld + 64 * k1 + l];
+          z[k] = fmaf(U.has[k] ? w : 0.f, ah, z[k]);
+        }
+      }
+    }
   }
+}
+
+// a = act(z), d = act'(z) of ONE of this lane's units under the live mask (U.live(k)): both 0 beyond the width.  A caller that
+// does not read d does not pay for it: everything here is inlined.  The loop over a lane's units is the caller's - as a loop over
+// arrays inside this function the softplus instances hold 3 to 5 more VGPRs, and the depth-two softplus search 73: 6 waves, not 7.
+template <int ACT>
+__device__ __forceinline__ void mlp_activate(const bool live, const float z, float &a, float &d) {
+  float ak, dk;
+  mlp_act<ACT>(z, ak, dk);
+  a = live ? ak : 0.f;
+  d = live ? dk : 0.f;
+}
+
+// element `lane` of W a + b (+ x when residual) over the last hidden layer's units (0 in lanes >= nx): one butterfly per output
+template <int UNITS>
+__device__ __forceinline__ float mlp_output_layer(const float *Ws, const int ld, const float *bs, const MlpUnits<UNITS> &U,
+                                                  const MlpModel &m, const int lane, const float tau, const float (&a)[UNITS]) {
   float next = 0.f;
   for (int i = 0; i < m.nx; ++i) {
     float part = 0.f;
 #pragma unroll
-    for (int k = 0; k < kMlpUnits; ++k) {
-      if (k < n_units) {
-        const float w = L.W2s[i * L.hp + row[k]];
-        part = fmaf(has[k] ? w : 0.f, a[k], part);
+    for (int k = 0; k < UNITS; ++k) {
+      if (k < U.n) {
+        const float w = Ws[i * ld + U.row[k]];
+        part = fmaf(U.has[k] ? w : 0.f, a[k], part);
       }
     }
-    float s = wave_sum64(part) + L.b2s[i];
+    float s = wave_sum64(part) + bs[i];
     if (m.residual) s += lane_value(tau, i);
     next = lane == i ? s : next;
   }
   return next;
 }
 
-// F = d next / d [x;u] (nx x ns, row-major) at Fp and into the wavefront's LDS, f = next - F tau at fq (lanes < nx).
-// VALU over LDS: d of every hidden unit goes to the wavefront's scratch, then lane e owns entries e, e + 64, ... of F
-// and sums over the hidden units in ascending order.  Within one wavefront LDS operations complete in program order; the
-// fences keep the compiler from moving a read above the write it depends on.
-__device__ __forceinline__ void mlp_jacobian_store(const MlpModel &m, const MlpLds &L, const int lane, const float tau,
-                                                   const float next, const float (&d)[kMlpUnits], float *Fp, float *fq) {
-  const int nx = m.nx, ns = m.nx + m.nu, H = m.n_hidden;
-  float *g = L.wave, *Fs = L.wave + kMlpMaxHidden;
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the previous step's reads of g and Fs are done)
+// N = W3 D2 W2 (nx x H1, row stride ld2) into the wavefront's slice, g2 = diag(D2) read from it: a lane owns columns lane,
+// lane + 64 (U: the units of layer 1) and takes the rows four at a time - per unit of layer 2 one d2, the lane's W2 entries
+// (consecutive lanes, consecutive words) and four W3 entries (one word for the wavefront) feed the fused multiply-adds; the
+// sum over the units of layer 2 ascending, a ragged last group of rows on clamped addresses.
+template <int UNITS>
+__device__ __forceinline__ void mlp_fold_output(const float *W3s, const int ld3, const float *g2, const float *W2s, const int ld2,
+                                                const MlpUnits<UNITS> &U, const int nx, const int H2, float *Ns) {
+  for (int i0 = 0; i0 < nx; i0 += 4) {
+    int r[4];
+    float acc[UNITS][4];
 #pragma unroll
-  for (int k = 0; k < kMlpUnits; ++k) {
-    const int h = lane + 64 * k;
-    if (h < H) g[h] = d[k];
+    for (int q = 0; q < 4; ++q) {
+      r[q] = (i0 + q < nx ? i0 + q : nx - 1) * ld3;
+#pragma unroll
+      for (int k = 0; k < UNITS; ++k) acc[k][q] = 0.f;
+    }
+    for (int h = 0; h < H2; ++h) {
+      const float dd = g2[h];
+      float w2[UNITS];
+#pragma unroll
+      for (int k = 0; k < UNITS; ++k) w2[k] = k < U.n ? W2s[h * ld2 + U.row[k]] : 0.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float w3d = W3s[r[q] + h] * dd;
+#pragma unroll
+        for (int k = 0; k < UNITS; ++k) acc[k][q] = fmaf(w3d, w2[k], acc[k][q]);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+      for (int k = 0; k < UNITS; ++k)
+        if (i0 + q < nx && k < U.n && U.has[k]) Ns[(i0 + q) * ld2 + U.row[k]] = acc[k][q];
+    }
   }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// F = left D1 W1 + [I|0] residual (nx x ns, row-major) at Fp and at Fs in the wavefront's slice, f = next - F tau at fq (lanes
+// < nx).  `left` (nx x H1, row stride ldl) is the network behind layer 1: the output layer's matrix at depth one, N at depth
+// two; g1 = diag(D1) from the slice.  VALU over LDS: lane e owns entries e, e + 64, ... of F and sums over the units of
+// layer 1 in ascending order.
+__device__ __forceinline__ void mlp_jacobian_tail(const MlpModel &m, const float *left, const int ldl, const float *g1, const float *W1s,
+                                                  const int nsp, float *Fs, const int lane, const float tau, const float next,
+                                                  float *Fp, float *fq) {
+  const int nx = m.nx, ns = m.nx + m.nu, H = m.H[0];
   for (int e = lane; e < nx * ns; e += 64) {
     const int i = e / ns, j = e % ns;
-    const float *w2 = L.W2s + i * L.hp, *w1 = L.W1s + j;
+    const float *lr = left + i * ldl, *w1 = W1s + j;
     float acc = (m.residual && i == j) ? 1.f : 0.f;
 #pragma unroll 4
-    for (int h = 0; h < H; ++h) acc = fmaf(w2[h] * g[h], w1[h * L.nsp], acc);
+    for (int h = 0; h < H; ++h) acc = fmaf(lr[h] * g1[h], w1[h * nsp], acc);
     Fs[e] = acc;
     Fp[e] = acc;
   }
@@ -212,220 +305,57 @@ __device__ __forceinline__ void mlp_jacobian_store(const MlpModel &m, const MlpL
   if (fq != nullptr && lane < nx) fq[lane] = f;
 }
 
-// ---------------------------------------------------------------------------------------------------- Depth two
-// The same layout: one wavefront per trajectory, four per workgroup, the weights staged once and one barrier.
-//     W1s [H1][ns | 1]   as above
-//     W2s [H2][H1 | 1]   lane l owns units l, l + 64 of layer 2 and walks ITS row: 64 rows on 64 banks
-//     W3s [nx][H2 | 1]   as W2s above
-//     b1s [H1], b2s [H2], b3s [nx]
-// 88.2 KB at the limits (nx 16, nu 8, H1 = H2 = 128).  A launch that forms Jacobians adds kMlp2WaveFloats (10.8 KB) per
-// wavefront: 131.5 KB, one workgroup per CU.  A layer-1 activation another lane needs is read from that lane's register
-// (v_readlane), so the step function touches no wavefront slice and the search without Jacobians has none.
-struct Mlp2Lds {
-  int nsp, hp1, hp2;                // row strides of W1s, W2s (and N) and W3s
-  float *W1s, *W2s, *W3s, *b1s, *b2s, *b3s, *wave;
-};
-
-__device__ __forceinline__ Mlp2Lds mlp2_stage(const MlpModel &m, float *lds) {
-  const int ns = m.nx + m.nu, H1 = m.n_hidden, H2 = m.n_hidden2;
-  Mlp2Lds L;
-  L.nsp = ns | 1;
-  L.hp1 = H1 | 1;
-  L.hp2 = H2 | 1;
-  L.W1s = lds;
-  L.W2s = L.W1s + H1 * L.nsp;
-  L.W3s = L.W2s + H2 * L.hp1;
-  L.b1s = L.W3s + m.nx * L.hp2;
-  L.b2s = L.b1s + H1;
-  L.b3s = L.b2s + H2;
-  L.wave = L.b3s + m.nx + (threadIdx.x / 64) * kMlp2WaveFloats;   // (only a launch that forms Jacobians has it)
-  const int tid = threadIdx.x, nt = blockDim.x;
-  for (int e = tid; e < H1 * ns; e += nt) L.W1s[(e / ns) * L.nsp + (e % ns)] = m.W1[e];
-  for (int e = tid; e < H2 * H1; e += nt) L.W2s[(e / H1) * L.hp1 + (e % H1)] = m.W2[e];
-  for (int e = tid; e < m.nx * H2; e += nt) L.W3s[(e / H2) * L.hp2 + (e % H2)] = m.W3[e];
-  for (int e = tid; e < H1; e += nt) L.b1s[e] = m.b1[e];
-  for (int e = tid; e < H2; e += nt) L.b2s[e] = m.b2[e];
-  for (int e = tid; e < m.nx; e += nt) L.b3s[e] = m.b3[e];
-  __syncthreads();
-  return L;
-}
-
-// ONE step of the two-layer model, the only place it is evaluated.  As mlp_next: explicit fmaf; layer-1 inputs ascending,
-// layer-2 inputs (the hidden units of layer 1) ascending, a lane's units ascending, one butterfly reduction per output;
-// units beyond H1 / H2 hold exact zeros and read clamped addresses.  Leaves this lane's act' of both layers in d1[], d2[].
-template <int ACT>
-__device__ __forceinline__ float mlp2_next(const MlpModel &m, const Mlp2Lds &L, const int lane, const float tau,
-                                           float (&d1)[kMlp2Units], float (&d2)[kMlp2Units]) {
-  const int ns = m.nx + m.nu, H1 = m.n_hidden, H2 = m.n_hidden2;
-  const int n1 = (H1 + 63) / 64, n2 = (H2 + 63) / 64;
-  int row1[kMlp2Units], row2[kMlp2Units];
-  bool has1[kMlp2Units], has2[kMlp2Units];
-  float z1[kMlp2Units], z2[kMlp2Units], a1[kMlp2Units], a2[kMlp2Units];
-#pragma unroll
-  for (int k = 0; k < kMlp2Units; ++k) {
-    const int h = lane + 64 * k;
-    has1[k] = h < H1;
-    row1[k] = has1[k] ? h : H1 - 1;
-    z1[k] = has1[k] ? L.b1s[row1[k]] : 0.f;
-    has2[k] = h < H2;
-    row2[k] = has2[k] ? h : H2 - 1;
-    z2[k] = has2[k] ? L.b2s[row2[k]] : 0.f;
-  }
-  for (int j = 0; j < ns; ++j) {
-    const float tj = lane_value(tau, j);
-#pragma unroll
-    for (int k = 0; k < kMlp2Units; ++k) {
-      if (k < n1) {
-        const float w = L.W1s[row1[k] * L.nsp + j];
-        z1[k] = fmaf(has1[k] ? w : 0.f, tj, z1[k]);
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kMlp2Units; ++k) {
-    float ak, dk;
-    mlp_act<ACT>(z1[k], ak, dk);
-    const bool live = k < n1 && has1[k];
-    a1[k] = live ? ak : 0.f;
-    d1[k] = live ? dk : 0.f;
-  }
-#pragma unroll
-  for (int k1 = 0; k1 < kMlp2Units; ++k1) {        // unit h = 64 k1 + l of layer 1 lives in a1[k1] of lane l
-    const int left = H1 - 64 * k1, cnt = left < 64 ? left : 64;
-    for (int l = 0; l < cnt; ++l) {
-      const float ah = lane_value(a1[k1], l);
-#pragma unroll
-      for (int k = 0; k < kMlp2Units; ++k) {
-        if (k < n2) {
-          const float w = L.W2s[row2[k] * L.hp1 + 64 * k1 + l];
-          z2[k] = fmaf(has2[k] ? w : 0.f, ah, z2[k]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < kMlp2Units; ++k) {
-    float ak, dk;
-    mlp_act<ACT>(z2[k], ak, dk);
-    const bool live = k < n2 && has2[k];
-    a2[k] = live ? ak : 0.f;
-    d2[k] = live ? dk : 0.f;
-  }
-  float next = 0.f;
-  for (int i = 0; i < m.nx; ++i) {
-    float part = 0.f;
-#pragma unroll
-    for (int k = 0; k < kMlp2Units; ++k) {
-      if (k < n2) {
-        const float w = L.W3s[i * L.hp2 + row2[k]];
-        part = fmaf(has2[k] ? w : 0.f, a2[k], part);
-      }
-    }
-    float s = wave_sum64(part) + L.b3s[i];
-    if (m.residual) s += lane_value(tau, i);
-    next = lane == i ? s : next;
-  }
-  return next;
-}
-
-// F = [I|0] residual + W3 D2 W2 D1 W1 at Fp, f = next - F tau at fq (lanes < nx).  VALU over LDS, in two products through the
-// wavefront's slice, every sum over hidden units ascending:
-//   N = W3 D2 W2 (nx x H1): a lane owns columns lane, lane + 64 and takes the rows four at a time - per unit of layer 2 one
-//       d2, the lane's two W2 entries (consecutive lanes, consecutive words) and four W3 entries (one word for the wavefront)
-//       feed eight fused multiply-adds;
-//   F = N D1 W1 + [I|0]: lane e owns entries e, e + 64, ... as in mlp_jacobian_store.
-__device__ __forceinline__ void mlp2_jacobian_store(const MlpModel &m, const Mlp2Lds &L, const int lane, const float tau,
-                                                    const float next, const float (&d1)[kMlp2Units],
-                                                    const float (&d2)[kMlp2Units], float *Fp, float *fq) {
-  const int nx = m.nx, ns = m.nx + m.nu, H1 = m.n_hidden, H2 = m.n_hidden2;
-  const int n1 = (H1 + 63) / 64;
-  float *g1 = L.wave, *g2 = g1 + kMlp2MaxHidden, *Ns = g2 + kMlp2MaxHidden, *Fs = Ns + kMlpMaxNx * (kMlp2MaxHidden | 1);
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the previous step's reads of the slice are done)
-  int col[kMlp2Units];
-  bool has[kMlp2Units];
-#pragma unroll
-  for (int k = 0; k < kMlp2Units; ++k) {
-    const int h = lane + 64 * k;
-    has[k] = h < H1;
-    col[k] = has[k] ? h : H1 - 1;
-    if (h < H1) g1[h] = d1[k];
-    if (h < H2) g2[h] = d2[k];
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  for (int i0 = 0; i0 < nx; i0 += 4) {
-    int r[4];
-    float acc[kMlp2Units][4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      r[q] = (i0 + q < nx ? i0 + q : nx - 1) * L.hp2;
-#pragma unroll
-      for (int k = 0; k < kMlp2Units; ++k) acc[k][q] = 0.f;
-    }
-    for (int h = 0; h < H2; ++h) {
-      const float dd = g2[h];
-      float w2[kMlp2Units];
-#pragma unroll
-      for (int k = 0; k < kMlp2Units; ++k) w2[k] = k < n1 ? L.W2s[h * L.hp1 + col[k]] : 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float w3d = L.W3s[r[q] + h] * dd;
-#pragma unroll
-        for (int k = 0; k < kMlp2Units; ++k) acc[k][q] = fmaf(w3d, w2[k], acc[k][q]);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-      for (int k = 0; k < kMlp2Units; ++k)
-        if (i0 + q < nx && k < n1 && has[k]) Ns[(i0 + q) * L.hp1 + col[k]] = acc[k][q];
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  for (int e = lane; e < nx * ns; e += 64) {
-    const int i = e / ns, j = e % ns;
-    const float *nr = Ns + i * L.hp1, *w1 = L.W1s + j;
-    float acc = (m.residual && i == j) ? 1.f : 0.f;
-#pragma unroll 4
-    for (int h = 0; h < H1; ++h) acc = fmaf(nr[h] * g1[h], w1[h * L.nsp], acc);
-    Fs[e] = acc;
-    Fp[e] = acc;
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  const int rr = lane < nx ? lane : 0;
-  float f = next;
-  for (int j = 0; j < ns; ++j) f = fmaf(-Fs[rr * ns + j], lane_value(tau, j), f);
-  if (fq != nullptr && lane < nx) fq[lane] = f;
-}
-
-// What the rollout and the search know of a network's depth: how its weights are staged, ONE step, that step's Jacobian.
+// What the rollout and the search know of a network: how its weights are staged, ONE step (the only place the network is
+// evaluated), that step's Jacobian.  d[l]: this lane's act' of hidden layer l + 1, left by `next` for `jacobian_store`.
 template <int DEPTH>
-struct MlpNet;
-template <>
-struct MlpNet<1> {
-  using Lds = MlpLds;
-  float a[kMlpUnits], d[kMlpUnits];
-  static __device__ __forceinline__ Lds stage(const MlpModel &m, float *lds) { return mlp_stage(m, lds); }
+struct MlpNet {
+  static_assert(DEPTH >= 1 && DEPTH <= kMlpMaxDepth, "depth");
+  static constexpr int UNITS = mlp_units(DEPTH);
+  using Lds = MlpLds<DEPTH>;
+  float d[DEPTH][UNITS];
+  static __device__ __forceinline__ Lds stage(const MlpModel &m, float *lds) { return mlp_stage<DEPTH>(m, lds); }
+
+  // tau: element `lane` of [x;u].  Returns element `lane` of the next state (0 in lanes >= nx).
   template <int ACT>
   __device__ __forceinline__ float next(const MlpModel &m, const Lds &L, const int lane, const float tau) {
-    return mlp_next<ACT>(m, L, lane, tau, a, d);
+    static_assert(DEPTH <= 2, "a third hidden layer is one more mlp_layer_from_units");
+    const MlpUnits<UNITS> U1(lane, m.H[0]), UL(lane, m.H[DEPTH - 1]);   // the units of layer 1 and of the last hidden layer
+    float a1[UNITS], a[UNITS], z[UNITS];
+    mlp_layer_from_lanes(L.W[0], L.ld[0], L.b[0], U1, m.nx + m.nu, tau, z);
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) mlp_activate<ACT>(U1.live(k), z[k], (DEPTH == 1 ? a : a1)[k], d[0][k]);
+    if constexpr (DEPTH == 2) {
+      mlp_layer_from_units(L.W[1], L.ld[1], L.b[1], UL, m.H[0], a1, z);
+#pragma unroll
+      for (int k = 0; k < UNITS; ++k) mlp_activate<ACT>(UL.live(k), z[k], a[k], d[1][k]);
+    }
+    return mlp_output_layer(L.W[DEPTH], L.ld[DEPTH], L.b[DEPTH], UL, m, lane, tau, a);
   }
-  __device__ __forceinline__ void jacobian_store(const MlpModel &m, const Lds &L, const int lane, const float tau,
-                                                 const float xn, float *Fp, float *fq) const {
-    mlp_jacobian_store(m, L, lane, tau, xn, d, Fp, fq);
-  }
-};
-template <>
-struct MlpNet<2> {
-  using Lds = Mlp2Lds;
-  float d1[kMlp2Units], d2[kMlp2Units];
-  static __device__ __forceinline__ Lds stage(const MlpModel &m, float *lds) { return mlp2_stage(m, lds); }
-  template <int ACT>
-  __device__ __forceinline__ float next(const MlpModel &m, const Lds &L, const int lane, const float tau) {
-    return mlp2_next<ACT>(m, L, lane, tau, d1, d2);
-  }
-  __device__ __forceinline__ void jacobian_store(const MlpModel &m, const Lds &L, const int lane, const float tau,
-                                                 const float xn, float *Fp, float *fq) const {
-    mlp2_jacobian_store(m, L, lane, tau, xn, d1, d2, Fp, fq);
+
+  // F = d next / d [x;u] at Fp, f = next - F tau at fq.  The slice: d of every hidden unit, layer by layer (g), depth two's N,
+  // then F.  Within one wavefront LDS operations complete in program order; the fences keep the compiler from moving a read
+  // above the write it depends on.
+  __device__ __forceinline__ void jacobian_store(const MlpModel &m, const Lds &L, const int lane, const float tau, const float xn,
+                                                 float *Fp, float *fq) const {
+    static_assert(DEPTH <= 2, "a third hidden layer folds through mlp_fold_output once more");
+    constexpr int HMAX = mlp_max_hidden(DEPTH);
+    float *g = L.wave, *Ns = g + DEPTH * HMAX, *Fs = DEPTH == 1 ? Ns : Ns + kMlpMaxNx * (HMAX | 1);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the previous step's reads of the slice are done)
+#pragma unroll
+    for (int k = 0; k < UNITS; ++k) {
+      const int h = lane + 64 * k;
+#pragma unroll
+      for (int l = 0; l < DEPTH; ++l)
+        if (h < m.H[l]) g[l * HMAX + h] = d[l][k];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    if constexpr (DEPTH == 1) {
+      mlp_jacobian_tail(m, L.W[1], L.ld[1], g, L.W[0], L.ld[0], Fs, lane, tau, xn, Fp, fq);
+    } else {
+      mlp_fold_output(L.W[2], L.ld[2], g + HMAX, L.W[1], L.ld[1], MlpUnits<UNITS>(lane, m.H[0]), m.nx, m.H[1], Ns);
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      mlp_jacobian_tail(m, Ns, L.ld[1], g, L.W[0], L.ld[0], Fs, lane, tau, xn, Fp, fq);
+    }
   }
 };
 
@@ -475,7 +405,7 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_rollout_linearize_kernel(c
 // pass cap.  a.F / a.f are not read.  The loop is wave-uniform by construction - a wavefront is one trajectory - so a
 // trajectory that has finished runs, stores and commits nothing more.
 // a.F_next (BoxDDP's chain): the accepted trajectory IS the next iteration's nominal one, so after the search the wavefront
-// walks it once more and stores its Jacobians, F_next [T-1,B,nx,ns] - through mlp_next and mlp_jacobian_store on the values
+// walks it once more and stores its Jacobians, F_next [T-1,B,nx,ns] - through MlpNet's next and jacobian_store on the values
 // mlp_rollout_linearize_kernel would start from, hence bit for bit what that kernel would store.  a.f_next, a.c_next: not written.
 // Depth two: the wavefront slices exist only when a.F_next is given (mlp_lds_bytes).
 template <int ACT, int DEPTH>
@@ -613,22 +543,16 @@ struct MlpGradArgs {
 template <int ACT>
 __global__ __launch_bounds__(64 * kMlpWaves) void mlp_param_grad_kernel(const MlpGradArgs a) {
   extern __shared__ float lds[];
-  const MlpLds L = mlp_stage(a.m, lds);
+  constexpr int UNITS = mlp_units(1);
+  const MlpLds<1> L = mlp_stage<1>(a.m, lds);
   const int lane = threadIdx.x % 64;
   const int w = blockIdx.x * kMlpWaves + threadIdx.x / 64;
   if (w >= a.G) return;      // (after the only barrier)
-  const int nx = a.m.nx, nu = a.m.nu, ns = nx + nu, H = a.m.n_hidden;
-  const int n_units = (H + 63) / 64;
+  const int nx = a.m.nx, nu = a.m.nu, ns = nx + nu, H = a.m.H[0];
   const int T = a.T;
   const size_t B = (size_t)a.B;
-  int row[kMlpUnits];
-  bool has[kMlpUnits];
-#pragma unroll
-  for (int k = 0; k < kMlpUnits; ++k) {
-    has[k] = lane + 64 * k < H;
-    row[k] = has[k] ? lane + 64 * k : H - 1;
-  }
-  float dW1[kMlpUnits][kMlpMaxNx + kMlpMaxNu] = {}, dW2[kMlpUnits][kMlpMaxNx] = {}, db1[kMlpUnits] = {}, db2 = 0.f;
+  const MlpUnits<UNITS> U(lane, H);
+  float dW1[UNITS][kMlpMaxNx + kMlpMaxNu] = {}, dW2[UNITS][kMlpMaxNx] = {}, db1[UNITS] = {}, db2 = 0.f;
 
   for (size_t b = w; b < B; b += a.G) {
     if (a.d_x_init != nullptr && lane < nx) a.d_x_init[b * nx + lane] = 0.f;
@@ -638,27 +562,29 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_param_grad_kernel(const Ml
       const size_t tb = (size_t)t * B + b;
       const float tau = lane < nx ? a.x[tb * nx + lane] : (lane < ns ? a.u[tb * nu + (lane - nx)] : 0.f);
       const float r = lane < nx ? a.grad_f[tb * nx + lane] : 0.f;
-      float act[kMlpUnits], dact[kMlpUnits];
-      (void)mlp_next<ACT>(a.m, L, lane, tau, act, dact);
+      float z[UNITS], act[UNITS], dact[UNITS];
+      mlp_layer_from_lanes(L.W[0], L.ld[0], L.b[0], U, ns, tau, z);
+#pragma unroll
+      for (int k = 0; k < UNITS; ++k) mlp_activate<ACT>(U.live(k), z[k], act[k], dact[k]);
       db2 += r;
-      float s[kMlpUnits] = {};                               // W2^T r at this lane's units
+      float s[UNITS] = {};                               // W2^T r at this lane's units
 #pragma unroll
       for (int i = 0; i < kMlpMaxNx; ++i) {
         if (i < nx) {
           const float ri = lane_value(r, i);
 #pragma unroll
-          for (int k = 0; k < kMlpUnits; ++k) {
-            if (k < n_units) {
-              const float w2 = L.W2s[i * L.hp + row[k]];
-              s[k] = fmaf(has[k] ? w2 : 0.f, ri, s[k]);
+          for (int k = 0; k < UNITS; ++k) {
+            if (k < U.n) {
+              const float w2 = L.W[1][i * L.ld[1] + U.row[k]];
+              s[k] = fmaf(U.has[k] ? w2 : 0.f, ri, s[k]);
               dW2[k][i] = fmaf(ri, act[k], dW2[k][i]);
             }
           }
         }
       }
-      float delta[kMlpUnits];
+      float delta[UNITS];
 #pragma unroll
-      for (int k = 0; k < kMlpUnits; ++k) {
+      for (int k = 0; k < UNITS; ++k) {
         delta[k] = dact[k] * s[k];
         db1[k] += delta[k];
       }
@@ -667,8 +593,8 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_param_grad_kernel(const Ml
         if (j < ns) {
           const float tj = lane_value(tau, j);
 #pragma unroll
-          for (int k = 0; k < kMlpUnits; ++k)
-            if (k < n_units) dW1[k][j] = fmaf(delta[k], tj, dW1[k][j]);
+          for (int k = 0; k < UNITS; ++k)
+            if (k < U.n) dW1[k][j] = fmaf(delta[k], tj, dW1[k][j]);
         }
       }
     }
@@ -677,7 +603,7 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mlp_param_grad_kernel(const Ml
   float *p = a.part + (size_t)w * mlp_grad_partial_floats(nx, nu, H);
   float *pb1 = p + H * ns, *pW2 = pb1 + H, *pb2 = pW2 + nx * H;
 #pragma unroll
-  for (int k = 0; k < kMlpUnits; ++k) {
+  for (int k = 0; k < UNITS; ++k) {
     const int h = lane + 64 * k;
     if (h < H) {
 #pragma unroll

@@ -10,13 +10,15 @@
 
 namespace dmpc {
 
-// One hidden layer (n_hidden2 == 0):  next = W2 act(W1 [x;u] + b1) + b2 (+ x), W2 [nx,H1].
-// Two (n_hidden2 = H2 >= 1):          next = W3 act(W2 act(W1 [x;u] + b1) + b2) + b3 (+ x), W2 [H2,H1], W3 [nx,H2].
+// DEPTH hidden layers (1 or 2) of widths H[0], H[1] and the output layer behind them: layer[l] has W [out_l, in_l] and b,
+//     in_0 = nx + nu, in_l = H[l-1];   out_l = H[l] for l < depth, nx for the output layer l = depth
+//     next = W[depth] act(... act(W[0] [x;u] + b[0]) ...) + b[depth] (+ x when residual)
+constexpr int kMlpMaxDepth = 2;
 struct MlpModel {
-  int nx, nu, n_hidden, residual;
-  const float *W1, *b1, *W2, *b2;   // [H1,ns], [H1], W2, its bias  (device pointers: an optimiser step is seen by the next launch)
-  int n_hidden2 = 0;
-  const float *W3 = nullptr, *b3 = nullptr;
+  int nx, nu, H[kMlpMaxDepth], residual, depth;
+  struct Layer {
+    const float *W, *b;   // device pointers: an optimiser step is seen by the next launch
+  } layer[kMlpMaxDepth + 1];
 };
 
 // The `n_hidden` argument of the C ABI is H1 | (H2 << 16) (DMPC_MLP_HIDDEN2 of include/dmpc.h); H2 = 0: one hidden layer.
@@ -27,13 +29,8 @@ inline int mlp_hidden2(int code) { return code >> 16; }
 inline MlpModel mlp_model(int nx, int nu, int code, int residual, const float *W1, const float *b1, const float *W2,
                           const float *b2) {
   const int H1 = mlp_hidden1(code), H2 = mlp_hidden2(code);
-  MlpModel m{nx, nu, H1, residual != 0 ? 1 : 0, W1, b1, W2, b2};
-  if (H2 > 0) {
-    m.n_hidden2 = H2;
-    m.W3 = W2 + (size_t)H2 * H1;
-    m.b3 = b2 + H2;
-  }
-  return m;
+  if (H2 == 0) return MlpModel{nx, nu, {H1, 0}, residual != 0 ? 1 : 0, 1, {{W1, b1}, {W2, b2}, {nullptr, nullptr}}};
+  return MlpModel{nx, nu, {H1, H2}, residual != 0 ? 1 : 0, 2, {{W1, b1}, {W2, b2}, {W2 + (size_t)H2 * H1, b2 + H2}}};
 }
 
 // the weights as ONE array (dmpc_box_ddp, dyn_kind 2): [W1 | b1 | W2 | b2], or [W1 | b1 | W2 | W3 | b2 | b3] - the tails
