@@ -1,4 +1,4 @@
-"""ctypes binding of libdmpc_hip.so (the C-ABI in include/dmpc.h).
+"""ctypes binding of libdmpc_hip.so (the C-ABI in include/dmpc.h and include/dmpc_mlp_grad.h).
 
 PyTorch is plumbing here: it owns device memory and the HIP stream; every solver call below is
 one C function taking raw device pointers.  There is NO CPU fallback: if the shared library is
@@ -91,6 +91,13 @@ SIGNATURES = {
                                       + [_c_f, _c_f, ctypes.c_float] + [_c_f, _c_sz, _c_f, _c_f]),
 }
 
+# include/dmpc_mlp_grad.h one to one: the weight gradient of a two-layer MlpDx, in the same library
+GRAD_SIGNATURES = {
+    "dmpc_mlp2_param_grad_partials": (_c_i, [_c_i]),
+    "dmpc_mlp2_param_grad_workspace_bytes": (_c_sz, [_c_i] * 4),
+    "dmpc_mlp2_param_grad": (_c_i, [_c_i] * 7 + [_c_f] * 13 + [_c_f, _c_sz, _c_f]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -112,7 +119,7 @@ def load(path=None):
                 "There is no CPU fallback." % (LIB_NAME, p, os.path.join(_HERE, "csrc", "build.py")))
         lib = ctypes.CDLL(p)
         partial = os.environ.get("DMPC_LIB_PARTIAL") == "1" and (path is not None or "DMPC_LIB" in os.environ)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()):
             if partial and not hasattr(lib, name):   # experiment builds of ONE translation unit (scripts/knob_variants.sh)
                 continue
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol

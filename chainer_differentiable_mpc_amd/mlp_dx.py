@@ -18,9 +18,12 @@ instead (`dmpc_box_ddp`, dyn_kind 2: the weights as one packed buffer, `packed_w
 GPU tensors, a supported size, a dense `QuadCost`, no `batch_coupled`; anything else keeps the host loop.
 
 Learning the weights follows mpc/approximate.py:77-119: the Jacobians F_t are constants of the graph, f_t = next - F_t [x;u]
-stays on it through `next` and the re-rolled states, and `MPCstep.backward`'s df reaches every weight.  By default that
-graph is a live torch rollout; with `device_grad=True` (one hidden layer only) it is one autograd node around the rollout's
-launch whose backward is `dmpc_mlp_param_grad` (one sweep kernel, one fixed-order reduction)."""
+stays on it through `next` and the re-rolled states, and `MPCstep.backward`'s df reaches every weight.  `param_grad` says
+where that gradient comes from: "live" (the default) is a live torch rollout on the graph - a Python loop of T - 1 steps;
+"device" is ONE autograd node around the rollout's launch whose backward is one sweep kernel and one fixed-order reduction,
+`dmpc_mlp_param_grad` with one hidden layer and `dmpc_mlp2_param_grad` (include/dmpc_mlp_grad.h) with two.  `device_grad=True`
+is the older spelling of `param_grad="device"` and serves one hidden layer only.  CPU tensors or a size outside the kernels'
+limits take the live route whatever the keyword says."""
 import math
 
 import torch
@@ -45,6 +48,7 @@ _ACT_FN = {
     "silu": (F_nn.silu, lambda z: torch.sigmoid(z) * (1.0 + z * (1.0 - torch.sigmoid(z)))),
     "softplus": (F_nn.softplus, torch.sigmoid),
 }
+PARAM_GRADS = ("live", "device")      # `param_grad`: where the weight gradient of `linearize`'s f comes from
 _ACT_OF_MODULE = {torch.nn.Tanh: "tanh", torch.nn.ReLU: "relu", torch.nn.SiLU: "silu", torch.nn.Softplus: "softplus"}
 
 
@@ -54,12 +58,15 @@ class MlpDx(torch.nn.Module):
     SEARCH_LINEARIZES = False
 
     def __init__(self, n_state, n_ctrl, n_hidden, residual=True, seed=None, device_grad=False, activation="tanh",
-                 device_loop=False):
+                 device_loop=False, param_grad="live"):
         super().__init__()
         if activation not in ACTIVATIONS:
             raise ValueError("MlpDx: unknown activation %r (one of %s)" % (activation, ", ".join(ACTIVATIONS)))
+        if param_grad not in PARAM_GRADS:
+            raise ValueError("MlpDx: param_grad is \"live\" or \"device\", found %r" % (param_grad,))
         self.activation = activation
-        self.device_grad = bool(device_grad)
+        # `device_grad`: the one-layer spelling of param_grad="device" from before the keyword existed; it implies it
+        self.param_grad = "device" if device_grad else param_grad
         # BoxDDP runs its iLQR loop as one chain of launches (`dmpc_box_ddp`, dyn_kind 2) where the chain serves the problem
         self.device_loop = bool(device_loop)
         self._packed = {}           # device -> the flat weight buffer of `packed_weights` (no parameter, no buffer, not pickled)
@@ -75,9 +82,9 @@ class MlpDx(torch.nn.Module):
             self.hidden = (self.n_hidden,)
         if min(self.hidden) < 1:
             raise ValueError("MlpDx: every hidden layer needs at least one unit, found %r" % (n_hidden,))
-        if self.depth == 2 and self.device_grad:
-            raise ValueError("MlpDx: device_grad=True serves one hidden layer only (dmpc_mlp_param_grad); a model with two "
-                             "takes its weight gradient from the default live route")
+        if self.depth == 2 and device_grad:
+            raise ValueError("MlpDx: device_grad=True serves one hidden layer only (dmpc_mlp_param_grad); for a model with two "
+                             "pass param_grad=\"device\" (dmpc_mlp2_param_grad)")
         self.residual = bool(residual)
         ns = self.n_state + self.n_ctrl
         gen = None if seed is None else torch.Generator().manual_seed(int(seed))
@@ -101,12 +108,24 @@ class MlpDx(torch.nn.Module):
         return len(self.hidden)
 
     @property
+    def device_grad(self):
+        """`param_grad == "device"` of a model with one hidden layer, under the name it had before `param_grad` existed;
+        assigning to it assigns `param_grad`"""
+        return self.depth == 1 and self.param_grad == "device"
+
+    @device_grad.setter
+    def device_grad(self, value):
+        if value and self.depth == 2:
+            raise ValueError("MlpDx: device_grad serves one hidden layer only; for a model with two set param_grad = \"device\"")
+        self.param_grad = "device" if value else "live"
+
+    @property
     def hidden_code(self):
         """the `n_hidden` argument of the C ABI: H, or DMPC_MLP_HIDDEN2(H1, H2)"""
         return self.hidden[0] if self.depth == 1 else _lib.mlp_hidden2(*self.hidden)
 
     @classmethod
-    def from_sequential(cls, net, n_state, n_ctrl, residual=True, device_grad=False, device_loop=False):
+    def from_sequential(cls, net, n_state, n_ctrl, residual=True, device_grad=False, device_loop=False, param_grad="live"):
         """the model of a trained `torch.nn.Sequential(Linear(n_state + n_ctrl, H), act, Linear(H, n_state))` whose input is
         [x;u], act one of Tanh, ReLU, SiLU, Softplus (beta = 1, threshold = 20).  The four tensors are copied; anything else is
         a ValueError that names what was found - a deeper network too: for two hidden layers construct
@@ -129,21 +148,27 @@ class MlpDx(torch.nn.Module):
             raise ValueError("MlpDx.from_sequential: want Linear(%d, H) and Linear(H, %d), found %s"
                              % (n_state + n_ctrl, n_state, found))
         m = cls(n_state, n_ctrl, l1.out_features, residual=residual, device_grad=device_grad, activation=name,
-                device_loop=device_loop)
+                device_loop=device_loop, param_grad=param_grad)
         with torch.no_grad():
             for p, q in zip(m._weights(), (l1.weight, l1.bias, l2.weight, l2.bias)):
                 p.copy_(q.detach())
         return m.to(device=l1.weight.device, dtype=l1.weight.dtype)
 
     def extra_repr(self):
-        return "n_state=%d, n_ctrl=%d, n_hidden=%s, residual=%s, activation=%s, device_grad=%s%s" % (
+        return "n_state=%d, n_ctrl=%d, n_hidden=%s, residual=%s, activation=%s, device_grad=%s%s%s" % (
             self.n_state, self.n_ctrl, self.n_hidden, self.residual, self.activation, self.device_grad,
-            ", device_loop=True" if self.device_loop else "")
+            ", device_loop=True" if self.device_loop else "",
+            ", param_grad=%s" % self.param_grad if self.param_grad != "live" else "")
 
     def __getstate__(self):
         state = self.__dict__.copy()
         state["_packed"] = {}       # a copy or an unpickled model packs into a buffer of its own
         return state
+
+    def __setstate__(self, state):
+        if "param_grad" not in state:       # pickled before the keyword existed: `device_grad` was a plain attribute
+            state["param_grad"] = "device" if state.pop("device_grad", False) else "live"
+        super().__setstate__(state)
 
     @property
     def act_code(self):
@@ -294,8 +319,8 @@ class MlpDx(torch.nn.Module):
     def linearize(self, x, u):
         """F_t = d next / d [x;u], f_t = next - F_t [x_t;u_t] along the trajectory re-rolled from x[0] (the contract of
         `PendulumDx.linearize`).  No gradient wanted: all of it from the kernel.  Otherwise F still comes from the kernel on
-        the GPU, next and the re-rolled states from a live torch rollout - or, with `device_grad`, f too comes from the
-        kernel and its gradient from `dmpc_mlp_param_grad`."""
+        the GPU, next and the re-rolled states from a live torch rollout - or, with `param_grad="device"`, f too comes from
+        the kernel and its gradient from `dmpc_mlp_param_grad` / `dmpc_mlp2_param_grad`."""
         T = x.shape[0]
         x0 = x[0]
         if self.fused_ok(x0, u):
@@ -304,8 +329,8 @@ class MlpDx(torch.nn.Module):
         if not self._grad_wanted(x0, u):
             _, F, f = self._rollout_linearize_torch(x0, u, True)
             return F, f
-        if self.device_grad and self.depth == 1 and self._on_device(x0, u):
-            return _DeviceLinearize.apply(self, *self._weights(), x0, u)
+        if self.param_grad == "device" and self._on_device(x0, u):
+            return _DeviceLinearize.apply(self, x0, u, *self._weights())
         F_dev = None
         if self._on_device(x0, u):
             F_dev = self.rollout_linearize(x0, u)[1]
@@ -324,15 +349,16 @@ class MlpDx(torch.nn.Module):
 
 
 class _DeviceLinearize(torch.autograd.Function):
-    """(F, f) of `MlpDx.linearize` as ONE node over (W1, b1, W2, b2, x[0], u): forward is the rollout's launch, backward
-    `dmpc_mlp_param_grad`.  F is a constant of the graph.  The weights are saved as autograd saves any input, so one
-    changed in place before the backward is autograd's version error, not a gradient at other weights than the forward's."""
+    """(F, f) of `MlpDx.linearize` as ONE node over (x[0], u, W1, b1, W2, b2[, W3, b3]): forward is the rollout's launch,
+    backward `dmpc_mlp_param_grad` or, with two hidden layers, `dmpc_mlp2_param_grad`.  F is a constant of the graph.  The
+    weights are saved as autograd saves any input, so one changed in place before the backward is autograd's version error,
+    not a gradient at other weights than the forward's."""
 
     @staticmethod
-    def forward(ctx, model, W1, b1, W2, b2, x0, u):
+    def forward(ctx, model, x0, u, *weights):
         x, F, f = model.rollout_linearize(x0, u)
         ctx.model = model
-        ctx.save_for_backward(W1, b1, W2, b2, x, u)
+        ctx.save_for_backward(x, u, *weights)
         ctx.mark_non_differentiable(F)
         return F, f
 
@@ -340,26 +366,34 @@ class _DeviceLinearize(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, _grad_F, grad_f):
         m = ctx.model
-        *weights, x, u = ctx.saved_tensors
+        x, u, *weights = ctx.saved_tensors
         T, B = u.shape[0], u.shape[1]
-        nx, nu, H = m.n_state, m.n_ctrl, m.hidden[0]
+        nx, nu = m.n_state, m.n_ctrl
         lib = _lib.load()
         d = u.device
-        W1, b1, W2, b2 = (_lib.f32c(p.detach(), d) for p in weights)
+        w = [_lib.f32c(p.detach(), d) for p in weights]
         xs, ud, g = _lib.f32c(x, d), _lib.f32c(u.detach(), d), _lib.f32c(grad_f, d)
         assert list(xs.shape) == [T, B, nx] and list(g.shape) == [max(T - 1, 0), B, nx]
         f32 = dict(dtype=torch.float32, device=d)
-        dW1, db1, dW2, db2 = (torch.empty(p.shape, **f32) for p in (W1, b1, W2, b2))
-        dx0 = torch.empty((B, nx), **f32) if ctx.needs_input_grad[5] else None
-        du = torch.empty((T, B, nu), **f32) if ctx.needs_input_grad[6] else None
-        nbytes = lib.dmpc_mlp_param_grad_workspace_bytes(B, nx, nu, H)
+        if m.depth == 2:
+            # the weights and their gradients as the two-layer entry points take them: [W2 | W3] and [b2 | b3]
+            entry, query = "dmpc_mlp2_param_grad", lib.dmpc_mlp2_param_grad_workspace_bytes
+            args = [w[0], w[1], torch.cat((w[2].reshape(-1), w[4].reshape(-1))), torch.cat((w[3], w[5]))]
+            outs = [torch.empty(a.shape, **f32) for a in args]
+            split = [outs[0], outs[1], outs[2][:w[2].numel()].view(w[2].shape), outs[3][:w[3].numel()],
+                     outs[2][w[2].numel():].view(w[4].shape), outs[3][w[3].numel():]]
+        else:
+            entry, query = "dmpc_mlp_param_grad", lib.dmpc_mlp_param_grad_workspace_bytes
+            args = w
+            split = outs = [torch.empty(a.shape, **f32) for a in args]
+        dx0 = torch.empty((B, nx), **f32) if ctx.needs_input_grad[1] else None
+        du = torch.empty((T, B, nu), **f32) if ctx.needs_input_grad[2] else None
+        nbytes = query(B, nx, nu, m.hidden_code)
         ws = _workspace(nbytes, d)
         with _lib.guard(d):
-            rc = lib.dmpc_mlp_param_grad(T, B, nx, nu, H, m.act_code, int(m.residual), _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2),
-                                         _lib.ptr(b2), _lib.ptr(xs), _lib.ptr(ud), _lib.ptr(g), _lib.ptr(dW1), _lib.ptr(db1),
-                                         _lib.ptr(dW2), _lib.ptr(db2), _lib.ptr(dx0), _lib.ptr(du), _lib.ptr(ws), nbytes,
-                                         _lib.stream_ptr(d))
-        _lib.check(rc, "dmpc_mlp_param_grad")
-        grads = [gr.to(p.dtype) if need else None
-                 for gr, p, need in zip((dW1, db1, dW2, db2), weights, ctx.needs_input_grad[1:5])]
-        return (None, *grads, None if dx0 is None else dx0.to(grad_f.dtype), None if du is None else du.to(u.dtype))
+            rc = getattr(lib, entry)(T, B, nx, nu, m.hidden_code, m.act_code, int(m.residual), *(_lib.ptr(a) for a in args),
+                                     _lib.ptr(xs), _lib.ptr(ud), _lib.ptr(g), *(_lib.ptr(o) for o in outs), _lib.ptr(dx0),
+                                     _lib.ptr(du), _lib.ptr(ws), nbytes, _lib.stream_ptr(d))
+        _lib.check(rc, entry)
+        grads = [gr.to(p.dtype) if need else None for gr, p, need in zip(split, weights, ctx.needs_input_grad[3:])]
+        return (None, None if dx0 is None else dx0.to(grad_f.dtype), None if du is None else du.to(u.dtype), *grads)

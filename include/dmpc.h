@@ -333,7 +333,7 @@ int dmpc_pendulum_rollout_linearize(int T, int B, const float *x_init, const flo
  *   cost difference, cap of 64 passes with DMPC_INFO_LS_ITERCAP, DMPC_INFO_NONFINITE) with the network in place of
  *   F_true, f_true.
  * dmpc_mlp_param_grad (one hidden layer only: a two-layer `n_hidden` is DMPC_E_UNSUPPORTED, its workspace query 0 - that
- *   gradient is taken by autograd through a live rollout): the gradient of a loss L(f) of dmpc_mlp_rollout_linearize's f with respect to the weights, F_t held
+ *   gradient is dmpc_mlp2_param_grad's, include/dmpc_mlp_grad.h, or autograd through a live rollout): the gradient of a loss L(f) of dmpc_mlp_rollout_linearize's f with respect to the weights, F_t held
  *   constant at the value of the live Jacobian (mpc/approximate.py:77-119).  x [T,B,nx] are the states that launch stored,
  *   grad_f [T-1,B,nx] = dL/df (may be NULL when T = 1).  dW1 [n_hidden,ns], db1 [n_hidden], dW2 [nx,n_hidden], db2 [nx] are
  *   WRITTEN (not added to): sum over t and b of r a_t^T, r, delta z_t^T, delta with r = grad_f_t and

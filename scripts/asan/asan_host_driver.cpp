@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include "dmpc.h"
+#include "dmpc_mlp_grad.h"
 
 static int checks = 0, bad = 0;
 #define EXPECT(cond)                                                   \
@@ -216,6 +217,21 @@ int main() {
         EXPECT(dmpc_mlp_param_grad_workspace_bytes(5, 16, 8, H) == 0);
         EXPECT(dmpc_mlp_param_grad(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, ws, 1 << 20, nullptr) ==
                DMPC_E_UNSUPPORTED);
+        // ... and dmpc_mlp2_param_grad (include/dmpc_mlp_grad.h) takes it, and refuses the one-layer code in turn
+        const size_t g2 = dmpc_mlp2_param_grad_workspace_bytes(5, 16, 8, H);
+        EXPECT(g2 == (ok ? (size_t)dmpc_mlp2_param_grad_partials(5) * (size_t)(H1 * 24 + H1 + H2 * H1 + 16 * H2 + H2 + 16) * sizeof(float) : 0));
+        const int rg2 = dmpc_mlp2_param_grad(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, ws, g2, nullptr);
+        EXPECT(ok ? rg2 >= 0 : rg2 == DMPC_E_UNSUPPORTED);
+        if (ok) {
+          EXPECT(dmpc_mlp2_param_grad(T, 5, 16, 8, H, 3, 1, p, p, nullptr, p, p, p, p, p, p, p, p, p, p, ws, g2, nullptr) == DMPC_E_BADARG);
+          EXPECT(dmpc_mlp2_param_grad(T, 5, 16, 8, H1, 3, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, ws, g2, nullptr) == DMPC_E_UNSUPPORTED);
+          if (T > 1) {
+            EXPECT(dmpc_mlp2_param_grad(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, nullptr, p, p, p, p, p, p, ws, g2, nullptr) == DMPC_E_BADARG);
+            EXPECT(dmpc_mlp2_param_grad(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, p, p, nullptr, nullptr, ws, g2 - 1, nullptr) ==
+                   DMPC_E_WORKSPACE);
+            EXPECT(dmpc_mlp2_param_grad(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, nullptr, g2, nullptr) == DMPC_E_WORKSPACE);
+          }
+        }
         const float mlp2[4] = {(float)H, 3.f, 1.f, 0.f};
         if (T > 1) {
           const int rm = dmpc_box_ddp(T, 4, 16, 8, p, p, p, p, nullptr, 2, mlp2, p, p, p, 1e-3f, 5, 0.2f, 10, 1e-3f, 3, 20, 0, 0, p, p, p,

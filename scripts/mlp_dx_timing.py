@@ -6,8 +6,9 @@ Medians over `--iters` solves after warm-up (device events around the whole solv
 kernel launches of one solve of each, and how far the two solutions' costs are apart.
 
 `--grad` times learning instead: one `BoxDDP(update_dynamics=True, detach_unconverged=False)` solve with grad enabled plus
-`backward` of sum(x) + sum(u), for `MlpDx(device_grad=True)` (the gradient node's backward is `dmpc_mlp_param_grad`) and
-`device_grad=False` (a live torch rollout and autograd through it: the baseline) on equal weights in the same run.
+`backward` of sum(x) + sum(u), for `MlpDx(param_grad="device")` (the gradient node's backward is `dmpc_mlp_param_grad`, with
+`--hidden2` `dmpc_mlp2_param_grad`; the output keys keep the name `device_grad`) and `param_grad="live"` (a live torch rollout
+and autograd through it: the baseline) on equal weights in the same run.
 
 `--chain` times the iLQR loop itself: the host loop (`MlpDx(device_loop=False)`, the default route) against `dmpc_box_ddp`'s
 chain with the network inside it (`device_loop=True`: `search_linearizes` 0 and 1 launched directly, and the hipGraph replay).
@@ -16,7 +17,8 @@ chain with the network inside it (`device_loop=True`: `search_linearizes` 0 and 
 the flag existed - another activation adds an "activation" key).
 
 `--hidden2 H2` makes every case a two-layer network: the H of `--cases` is its first width, H2 its second ("n_hidden" is then
-the pair).  The run fails if the device route is not faster than the plain callable measured beside it.
+the pair).  The run fails if the device route is not faster than the plain callable measured beside it; with `--grad`, if
+solve + backward on the device route is slower than on the live route of the same run.
 
     python scripts/mlp_dx_timing.py [--grad | --chain] [--iters 20] [--warmup 3] [--cases 3x1x32,8x2x64] [--batch 128] [--horizon 20]
                                     [--activation tanh] [--hidden2 H2] [--json out]"""
@@ -136,7 +138,7 @@ def run_grad_case(nx, nu, H, B, T, iters, warmup, activation="tanh"):
         out["activation"] = activation
     routes = {}
     for tag, flag in (("device_grad", True), ("live", False)):
-        m = MlpDx(nx, nu, H, seed=0, device_grad=flag, activation=activation).cuda()
+        m = MlpDx(nx, nu, H, seed=0, param_grad="device" if flag else "live", activation=activation).cuda()
         solver = BoxDDP(T, -0.5, 0.5, B, nx, nu, None, max_iter=10, quiet=True, update_dynamics=True, detach_unconverged=False)
         routes[tag] = (m, solver, [], [])
 
@@ -200,6 +202,8 @@ def main():
         res.append(r)
         if a.hidden2 > 0 and not (a.chain or a.grad):
             assert r["device_ms"] < r["callable_ms"], "the device route is not faster than the plain callable"
+        if a.hidden2 > 0 and a.grad:
+            assert r["device_grad_ms"] <= r["live_ms"], "the device gradient route is slower than the live route"
     if a.json:
         with open(a.json, "w") as fh:
             json.dump(res, fh, indent=1)
