@@ -1,4 +1,4 @@
-"""ctypes binding of libdmpc_hip.so (the C-ABI in include/dmpc.h and include/dmpc_mlp_grad.h).
+"""ctypes binding of libdmpc_hip.so (the C-ABI in include/dmpc.h, include/dmpc_mlp_grad.h and include/dmpc_episode.h).
 
 PyTorch is plumbing here: it owns device memory and the HIP stream; every solver call below is
 one C function taking raw device pointers.  There is NO CPU fallback: if the shared library is
@@ -98,6 +98,14 @@ GRAD_SIGNATURES = {
     "dmpc_mlp2_param_grad": (_c_i, [_c_i] * 7 + [_c_f] * 13 + [_c_f, _c_sz, _c_f]),
 }
 
+# include/dmpc_episode.h one to one: a closed-loop MPC episode as one chain of launches, in the same library
+EPISODE_SIGNATURES = {
+    "dmpc_mpc_episode_workspace_bytes": (_c_sz, [_c_i] * 4),
+    "dmpc_mpc_episode": (_c_i, [_c_i] * 5 + [_c_f] * 5 + [_c_i, _c_f] + [_c_f, _c_f, _c_i, _c_f] + [_c_f] * 3 +
+                         [ctypes.c_float, _c_i, ctypes.c_float, _c_i, ctypes.c_float, _c_i, _c_i, _c_i] +
+                         [_c_f] * 7 + [_c_sz, _c_f, _c_f]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -119,7 +127,7 @@ def load(path=None):
                 "There is no CPU fallback." % (LIB_NAME, p, os.path.join(_HERE, "csrc", "build.py")))
         lib = ctypes.CDLL(p)
         partial = os.environ.get("DMPC_LIB_PARTIAL") == "1" and (path is not None or "DMPC_LIB" in os.environ)
-        for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(EPISODE_SIGNATURES.items()):
             if partial and not hasattr(lib, name):   # experiment builds of ONE translation unit (scripts/knob_variants.sh)
                 continue
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol

@@ -22,6 +22,17 @@ namespace dmpc {
 
 enum { kDdpDone = 0, kDdpIter = 1, kDdpStatus = 2, kDdpNotImproved = 3 };
 
+// Row i of a LinDx step, x_{t+1}[i] = F_t[i,:] [x_t; u_t] + f_t[i]: f first, then the states, then the controls, ascending -
+// THE summation order of the rollout below and of whoever else steps a linear model (the episode's plant, episode_kernels.hpp)
+__device__ __forceinline__ float lin_step_row(const float *Ft, const int i, const float *xt, const float *ut, const int nx,
+                                              const int nu, const float f0) {
+  const int ns = nx + nu;
+  float acc = f0;
+  for (int j = 0; j < nx; ++j) acc = fmaf(Ft[i * ns + j], xt[j], acc);
+  for (int j = 0; j < nu; ++j) acc = fmaf(Ft[i * ns + nx + j], ut[j], acc);
+  return acc;
+}
+
 __global__ __launch_bounds__(64) void lin_rollout_kernel(int T, int B, int nx, int nu, const float *__restrict__ x_init,
                                                          const float *__restrict__ u, const float *__restrict__ F,
                                                          const float *__restrict__ f, float *__restrict__ x,
@@ -37,12 +48,7 @@ __global__ __launch_bounds__(64) void lin_rollout_kernel(int T, int B, int nx, i
     const size_t tb = (size_t)t * Bs + b;
     const float *xt = x + tb * nx, *ut = u + tb * nu, *Ft = F + tb * nx * ns;
     float *xn = x + (tb + Bs) * nx;
-    for (int i = 0; i < nx; ++i) {
-      float acc = f != nullptr ? f[tb * nx + i] : 0.f;
-      for (int j = 0; j < nx; ++j) acc = fmaf(Ft[i * ns + j], xt[j], acc);
-      for (int j = 0; j < nu; ++j) acc = fmaf(Ft[i * ns + nx + j], ut[j], acc);
-      xn[i] = acc;
-    }
+    for (int i = 0; i < nx; ++i) xn[i] = lin_step_row(Ft, i, xt, ut, nx, nu, f != nullptr ? f[tb * nx + i] : 0.f);
   }
 }
 

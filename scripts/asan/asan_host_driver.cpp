@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include "dmpc.h"
 #include "dmpc_mlp_grad.h"
+#include "dmpc_episode.h"
 
 static int checks = 0, bad = 0;
 #define EXPECT(cond)                                                   \
@@ -239,6 +240,52 @@ int main() {
           EXPECT(ok ? rm >= 0 : rm == DMPC_E_UNSUPPORTED);
         }
       }
+  // the closed-loop episode (include/dmpc_episode.h): its own checks first, then dmpc_box_ddp's; the workspace arithmetic
+  {
+    const float pend[6] = {10.f, 1.f, 1.f, 0.05f, 2.f, 1.f};
+    auto episode = [&](int n_steps, int T, int B, int nx, int nu, const float *F, int dyn_kind, const float *dyn_params, const float *plant_F,
+                       const float *plant_f, int plant_kind, const float *plant_params, void *w, size_t short_by) {
+      return dmpc_mpc_episode(n_steps, T, B, nx, nu, p, p, p, F, nullptr, dyn_kind, dyn_params, plant_F, plant_f, plant_kind, plant_params,
+                              p, p, p, 1e-3f, 5, 0.2f, 10, 1e-4f, 3, 20, 1, p, p, p, nullptr, nullptr, pi, w,
+                              dmpc_mpc_episode_workspace_bytes(T, B, nx, nu) - short_by, nullptr, nullptr);
+    };
+    EXPECT(dmpc_mpc_episode_workspace_bytes(0, 4, 3, 1) == 0 && dmpc_mpc_episode_workspace_bytes(4, 4, 3, 0) == 0);
+    for (auto &s : shapes)
+      for (int T : {2, 20, 400})
+        for (int B : {1, 3, 4, 17, 4096}) {
+          const int nx = s[0], nu = s[1];
+          const size_t eb = dmpc_mpc_episode_workspace_bytes(T, B, nx, nu);
+          EXPECT(eb >= dmpc_box_ddp_workspace_bytes(T, B, nx, nu) + sizeof(float) * ((size_t)B * nx + (size_t)T * B * (nx + 2 * nu) + 4 * (size_t)B + 8));
+          EXPECT(eb % 16 == 0);
+          const int r = episode(2, T, B, nx, nu, p, 0, nullptr, p, p, 0, nullptr, ws, 0);
+          EXPECT(nx + nu > 64 ? r == DMPC_E_UNSUPPORTED : (r >= 0 || r == DMPC_E_UNSUPPORTED));   // (launches fail: no device)
+          EXPECT(episode(2, T, B, nx, nu, p, 0, nullptr, p, p, 0, nullptr, ws, 1) == (nx + nu > 64 ? DMPC_E_UNSUPPORTED : DMPC_E_WORKSPACE));
+          const int rp = episode(2, T, B, nx, nu, p, 0, nullptr, nullptr, nullptr, 1, pend, ws, 0);
+          EXPECT(nx == 3 && nu == 1 ? rp >= 0 : rp == DMPC_E_UNSUPPORTED);
+        }
+    EXPECT(episode(0, 4, 2, 3, 1, p, 0, nullptr, p, nullptr, 0, nullptr, ws, 0) == DMPC_E_BADARG);
+    EXPECT(episode(2, 1, 2, 3, 1, p, 0, nullptr, p, nullptr, 0, nullptr, ws, 0) == DMPC_E_BADARG);
+    EXPECT(episode(2, 4, 0, 3, 1, p, 0, nullptr, p, nullptr, 0, nullptr, ws, 0) == DMPC_E_BADARG);
+    EXPECT(episode(2, 4, 2, 3, 1, p, 0, nullptr, nullptr, nullptr, 0, nullptr, ws, 0) == DMPC_E_BADARG);
+    EXPECT(episode(2, 4, 2, 3, 1, p, 0, nullptr, p, nullptr, 0, nullptr, nullptr, 0) == DMPC_E_BADARG);
+    EXPECT(episode(2, 4, 2, 3, 1, p, 0, nullptr, p, nullptr, 3, nullptr, ws, 0) == DMPC_E_UNSUPPORTED);
+    EXPECT(episode(2, 4, 2, 3, 1, p, 0, nullptr, nullptr, nullptr, 1, nullptr, ws, 0) == DMPC_E_BADARG);
+    EXPECT(episode(2, 4, 2, 3, 1, nullptr, 0, nullptr, p, nullptr, 0, nullptr, ws, 0) == DMPC_E_BADARG);        // (dmpc_box_ddp's)
+    EXPECT(episode(2, 4, 2, 3, 1, p, 3, nullptr, p, nullptr, 0, nullptr, ws, 0) == DMPC_E_UNSUPPORTED);         // (dmpc_box_ddp's)
+    EXPECT(episode(2, 4, 2, 3, 1, nullptr, 1, pend, nullptr, nullptr, 1, pend, ws, 0) >= 0);
+    for (int H1 : {0, 1, 5, 128, 129, 256, 257})
+      for (int H2 : {0, 7, 128, 129}) {
+        const float net[4] = {(float)DMPC_MLP_HIDDEN2(H1, H2), 3.f, 1.f, 0.f};
+        const bool ok = dmpc_mlp_dx_supported(16, 8, DMPC_MLP_HIDDEN2(H1, H2), 3) == 1;
+        const int rn = episode(2, 5, 3, 16, 8, p, 2, net, p, nullptr, 2, net, ws, 0);      // the network as model and as plant
+        EXPECT(ok ? rn >= 0 : rn == DMPC_E_UNSUPPORTED);
+        EXPECT(episode(2, 5, 3, 16, 8, p, 0, nullptr, p, p, 2, net, ws, 0) == DMPC_E_BADARG);                   // plant_f with a network
+        if (ok) EXPECT(episode(2, 5, 3, 16, 8, p, 2, net, p, nullptr, 2, net, ws, 1) == DMPC_E_WORKSPACE);
+      }
+    const float frac[3] = {5.5f, 0.f, 1.f}, neg[3] = {5.f, -1.f, 1.f}, res[3] = {5.f, 0.f, 0.5f};
+    for (const float *bad_params : {frac, neg, res})
+      EXPECT(episode(2, 4, 2, 3, 1, p, 0, nullptr, p, nullptr, 2, bad_params, ws, 0) == DMPC_E_BADARG);
+  }
   EXPECT(dmpc_mlp_param_grad_partials(0) == 0 && dmpc_mlp_param_grad_partials(1 << 30) == dmpc_mlp_param_grad_partials(1 << 20));
   EXPECT(dmpc_lqr_shared_workspace_bytes(0, 1, 1, 1) == 0 && dmpc_lqr_shared_saved_bytes(0, 1, 1) == 0);
   EXPECT(dmpc_lqr_kernel_family(0, 3) == DMPC_E_UNSUPPORTED);
