@@ -1,4 +1,5 @@
-"""ctypes binding of libdmpc_hip.so (the C-ABI in include/dmpc.h, include/dmpc_mlp_grad.h and include/dmpc_episode.h).
+"""ctypes binding of libdmpc_hip.so (the C-ABI in include/dmpc.h, include/dmpc_mlp_grad.h, include/dmpc_episode.h and
+include/dmpc_mlp_rollout_grad.h).
 
 PyTorch is plumbing here: it owns device memory and the HIP stream; every solver call below is
 one C function taking raw device pointers.  There is NO CPU fallback: if the shared library is
@@ -106,6 +107,13 @@ EPISODE_SIGNATURES = {
                          [_c_f] * 7 + [_c_sz, _c_f, _c_f]),
 }
 
+# include/dmpc_mlp_rollout_grad.h one to one: the vector-Jacobian product of the MlpDx rollout, in the same library
+ROLLOUT_GRAD_SIGNATURES = {
+    "dmpc_mlp_rollout_grad_partials": (_c_i, [_c_i, _c_i]),
+    "dmpc_mlp_rollout_grad_workspace_bytes": (_c_sz, [_c_i] * 4),
+    "dmpc_mlp_rollout_grad": (_c_i, [_c_i] * 7 + [_c_f] * 13 + [_c_f, _c_sz, _c_f]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -127,7 +135,8 @@ def load(path=None):
                 "There is no CPU fallback." % (LIB_NAME, p, os.path.join(_HERE, "csrc", "build.py")))
         lib = ctypes.CDLL(p)
         partial = os.environ.get("DMPC_LIB_PARTIAL") == "1" and (path is not None or "DMPC_LIB" in os.environ)
-        for name, (res, args) in list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(EPISODE_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(EPISODE_SIGNATURES.items())
+                                   + list(ROLLOUT_GRAD_SIGNATURES.items())):
             if partial and not hasattr(lib, name):   # experiment builds of ONE translation unit (scripts/knob_variants.sh)
                 continue
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol

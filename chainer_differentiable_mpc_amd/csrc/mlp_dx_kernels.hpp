@@ -22,6 +22,8 @@
 //                                  mpc_generic_forward_kernel, the dynamics evaluated in place of F tau + f.
 //   mlp_param_grad_kernel,         the gradient of a loss of the rollout's f with respect to W1, b1, W2, b2 (depth one): per-wavefront
 //   mlp_param_grad_reduce_kernel   sums in registers, then a fixed-order reduction of the partials (at the end of this file).
+//                                  The same sweeps with the co-state carried, for a loss of the rolled states themselves, are
+//                                  siblings in mlp_rollout_grad_kernels.hpp; they store these partials for these reductions.
 //
 // Layout.  Runtime dimensions (nx <= 16, nu <= 8), ONE wavefront per trajectory, four per workgroup.  The weights are
 // staged into LDS once per workgroup (mlp_stage) and shared by its wavefronts - the matrices in layer order, then the biases:

@@ -23,7 +23,14 @@ where that gradient comes from: "live" (the default) is a live torch rollout on 
 "device" is ONE autograd node around the rollout's launch whose backward is one sweep kernel and one fixed-order reduction,
 `dmpc_mlp_param_grad` with one hidden layer and `dmpc_mlp2_param_grad` (include/dmpc_mlp_grad.h) with two.  `device_grad=True`
 is the older spelling of `param_grad="device"` and serves one hidden layer only.  CPU tensors or a size outside the kernels'
-limits take the live route whatever the keyword says."""
+limits take the live route whatever the keyword says.
+
+Fitting the network to recorded trajectories: `rollout(x_init, u)` is the multi-step prediction xhat_{t+1} = next(xhat_t, u_t)
+and `prediction_loss(x, u, horizon, weight)` its mean squared error against the record over windows of `horizon` steps
+(`ClosedLoop`'s `EpisodeOut.x`, `EpisodeOut.u` go in as they are).  In that loss the co-state is NOT zero - it back-propagates
+through time.  With `param_grad="device"` `rollout` is one autograd node: forward the rollout's launch, backward
+`dmpc_mlp_rollout_grad` (include/dmpc_mlp_rollout_grad.h), one reverse-sweep kernel that carries the co-state and the weight
+gradient's fixed-order reduction, with gradients to every weight, x_init and u.  "live" (the default) is the torch loop."""
 import math
 
 import torch
@@ -347,6 +354,72 @@ class MlpDx(torch.nn.Module):
             return F, f
         return torch.stack(Fs, 0), torch.stack(fs, 0)
 
+    # ------------------------------------------------------------------ fitting the network to trajectories
+    def rollout(self, x_init, u, T=None):
+        """x [T,B,nx] with x[0] = x_init [B,nx], x[t+1] = next(x[t], u[t]).  `u` [T,B,nu] or [T-1,B,nu]: its row T-1 is never
+        read; T = u.shape[0] unless given (then u has T or T - 1 rows).  Three routes:
+          no gradient wanted                      the one-launch rollout, `rollout_linearize(x_init, u, want_model=False)[0]`
+          a gradient wanted, param_grad="device",
+          GPU tensors, a supported size           ONE autograd node: forward that same launch - the states are bit-equal to what
+                                                  the solver's rollout sees - backward `dmpc_mlp_rollout_grad`, one reverse sweep
+                                                  that carries the co-state; gradients reach the weights, x_init and u
+          otherwise                               the torch loop over `_step`, autograd through every step"""
+        T = u.shape[0] if T is None else int(T)
+        if T < 1 or u.shape[0] not in (T, T - 1):
+            raise ValueError("MlpDx.rollout: u has %d rows, want T = %d or T - 1" % (u.shape[0], T))
+        assert x_init.shape[-1] == self.n_state and u.shape[-1] == self.n_ctrl and tuple(u.shape[1:-1]) == tuple(x_init.shape[:-1])
+        if not self._grad_wanted(x_init, u):
+            return self.rollout_linearize(x_init, _rows(u, T), want_model=False)[0]
+        if self.param_grad == "device" and self._on_device(x_init, u):
+            return _DeviceRollout.apply(self, T, x_init, u, *self._weights())
+        xs = [x_init]
+        for t in range(T - 1):
+            xs.append(self._step(xs[t], u[t])[0])
+        return torch.stack(xs, 0)
+
+    def prediction_loss(self, x, u, horizon=None, weight=None):
+        """Multi-step prediction error along recorded trajectories x [T,B,nx], u [T,B,nu] or [T-1,B,nu] (`EpisodeOut.x` and
+        `EpisodeOut.u` as they are): the mean of weight_i (xhat - x)_i^2 over windows, steps >= 1 and components i, xhat rolled
+        from the record's state at the window's start under the record's controls.
+          horizon=None   one window from x[0] over the whole record
+          horizon=h      1 <= h <= T - 1: a window from every t = 0 .. T-1-h, each rolled h steps; h = 1 is one-step teacher forcing
+        The windows are folded into the batch axis start-major (row start * B + b) and go through `rollout` as one batch: with
+        param_grad="device" the network runs in one launch forward and two backward, whatever T and h; the rest is plain torch.
+        `weight` [nx] or None."""
+        T = x.shape[0]
+        if x.dim() != 3 or u.dim() != 3 or u.shape[0] not in (T, T - 1):
+            raise ValueError("MlpDx.prediction_loss: x [T,B,nx] and u [T,B,nu] or [T-1,B,nu], found %s and %s"
+                             % (tuple(x.shape), tuple(u.shape)))
+        h = T - 1 if horizon is None else int(horizon)
+        if h < 1 or h > T - 1:
+            raise ValueError("MlpDx.prediction_loss: horizon must be in 1 .. T - 1 = %d, found %r" % (T - 1, horizon))
+        n_w, B = T - h, x.shape[1]
+        x0 = x[:n_w].reshape(n_w * B, self.n_state)
+        uw = torch.stack([u[s:s + n_w] for s in range(h)], 0).reshape(h, n_w * B, self.n_ctrl)
+        target = torch.stack([x[s:s + n_w] for s in range(1, h + 1)], 0).reshape(h, n_w * B, self.n_state)
+        err = (self.rollout(x0, uw, T=h + 1)[1:] - target) ** 2
+        if weight is not None:
+            err = err * torch.as_tensor(weight, dtype=err.dtype, device=err.device)
+        return err.mean()
+
+
+def _rows(u, T):
+    """u with T rows: a zero row behind one that has T - 1 (the row is never read)"""
+    return u if u.shape[0] == T else torch.cat((u, u.new_zeros((1,) + tuple(u.shape[1:]))), 0)
+
+
+def _packed_grads(depth, w):
+    """(args, outs, split) for the gradient entry points: the weights `w` as they take them - two hidden layers: [W2 | W3] and
+    [b2 | b3] - empty outputs of those shapes, and views of the outputs in the order and shapes of `w`"""
+    if depth == 2:
+        args = [w[0], w[1], torch.cat((w[2].reshape(-1), w[4].reshape(-1))), torch.cat((w[3], w[5]))]
+        outs = [torch.empty_like(a) for a in args]
+        split = [outs[0], outs[1], outs[2][:w[2].numel()].view(w[2].shape), outs[3][:w[3].numel()],
+                 outs[2][w[2].numel():].view(w[4].shape), outs[3][w[3].numel():]]
+        return args, outs, split
+    outs = [torch.empty_like(a) for a in w]
+    return w, outs, outs
+
 
 class _DeviceLinearize(torch.autograd.Function):
     """(F, f) of `MlpDx.linearize` as ONE node over (x[0], u, W1, b1, W2, b2[, W3, b3]): forward is the rollout's launch,
@@ -376,16 +449,10 @@ class _DeviceLinearize(torch.autograd.Function):
         assert list(xs.shape) == [T, B, nx] and list(g.shape) == [max(T - 1, 0), B, nx]
         f32 = dict(dtype=torch.float32, device=d)
         if m.depth == 2:
-            # the weights and their gradients as the two-layer entry points take them: [W2 | W3] and [b2 | b3]
             entry, query = "dmpc_mlp2_param_grad", lib.dmpc_mlp2_param_grad_workspace_bytes
-            args = [w[0], w[1], torch.cat((w[2].reshape(-1), w[4].reshape(-1))), torch.cat((w[3], w[5]))]
-            outs = [torch.empty(a.shape, **f32) for a in args]
-            split = [outs[0], outs[1], outs[2][:w[2].numel()].view(w[2].shape), outs[3][:w[3].numel()],
-                     outs[2][w[2].numel():].view(w[4].shape), outs[3][w[3].numel():]]
         else:
             entry, query = "dmpc_mlp_param_grad", lib.dmpc_mlp_param_grad_workspace_bytes
-            args = w
-            split = outs = [torch.empty(a.shape, **f32) for a in args]
+        args, outs, split = _packed_grads(m.depth, w)
         dx0 = torch.empty((B, nx), **f32) if ctx.needs_input_grad[1] else None
         du = torch.empty((T, B, nu), **f32) if ctx.needs_input_grad[2] else None
         nbytes = query(B, nx, nu, m.hidden_code)
@@ -397,3 +464,42 @@ class _DeviceLinearize(torch.autograd.Function):
         _lib.check(rc, entry)
         grads = [gr.to(p.dtype) if need else None for gr, p, need in zip(split, weights, ctx.needs_input_grad[3:])]
         return (None, None if dx0 is None else dx0.to(grad_f.dtype), None if du is None else du.to(u.dtype), *grads)
+
+
+class _DeviceRollout(torch.autograd.Function):
+    """x of `MlpDx.rollout` as ONE node over (x_init, u, W1, b1, W2, b2[, W3, b3]): forward is the rollout's launch without its
+    Jacobians, backward `dmpc_mlp_rollout_grad` (include/dmpc_mlp_rollout_grad.h) on the states that launch stored.  The weights
+    are saved as autograd saves any input, so one changed in place before the backward is autograd's version error."""
+
+    @staticmethod
+    def forward(ctx, model, T, x_init, u, *weights):
+        x = model.rollout_linearize(x_init, _rows(u, T), want_model=False)[0]
+        ctx.model = model
+        ctx.save_for_backward(x, u, *weights)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_x):
+        m = ctx.model
+        x, u, *weights = ctx.saved_tensors
+        T, B = x.shape[0], x.shape[1]
+        nx, nu = m.n_state, m.n_ctrl
+        lib = _lib.load()
+        d = x.device
+        w = [_lib.f32c(p.detach(), d) for p in weights]
+        xs, ud, g = _lib.f32c(x, d), _lib.f32c(_rows(u.detach(), T), d), _lib.f32c(grad_x, d)
+        assert list(xs.shape) == [T, B, nx] and list(ud.shape) == [T, B, nu] and list(g.shape) == [T, B, nx]
+        f32 = dict(dtype=torch.float32, device=d)
+        args, outs, split = _packed_grads(m.depth, w)
+        dx0 = torch.empty((B, nx), **f32) if ctx.needs_input_grad[2] else None
+        du = torch.empty((T, B, nu), **f32) if ctx.needs_input_grad[3] else None
+        nbytes = lib.dmpc_mlp_rollout_grad_workspace_bytes(B, nx, nu, m.hidden_code)
+        ws = _workspace(nbytes, d)
+        with _lib.guard(d):
+            rc = lib.dmpc_mlp_rollout_grad(T, B, nx, nu, m.hidden_code, m.act_code, int(m.residual), *(_lib.ptr(a) for a in args),
+                                           _lib.ptr(xs), _lib.ptr(ud), _lib.ptr(g), *(_lib.ptr(o) for o in outs), _lib.ptr(dx0),
+                                           _lib.ptr(du), _lib.ptr(ws), nbytes, _lib.stream_ptr(d))
+        _lib.check(rc, "dmpc_mlp_rollout_grad")
+        grads = [gr.to(p.dtype) if need else None for gr, p, need in zip(split, weights, ctx.needs_input_grad[4:])]
+        return (None, None, None if dx0 is None else dx0.to(grad_x.dtype), None if du is None else du[:u.shape[0]].to(u.dtype), *grads)

@@ -9,6 +9,7 @@
 #include "dmpc.h"
 #include "dmpc_mlp_grad.h"
 #include "dmpc_episode.h"
+#include "dmpc_mlp_rollout_grad.h"
 
 static int checks = 0, bad = 0;
 #define EXPECT(cond)                                                   \
@@ -201,6 +202,22 @@ int main() {
               EXPECT(dmpc_mlp_param_grad(T, 5, nx, nu, H, 0, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, nullptr, gwb, nullptr) ==
                      DMPC_E_WORKSPACE);
             }
+            // the rollout's vector-Jacobian product (include/dmpc_mlp_rollout_grad.h): the same checks, the same workspace
+            EXPECT(dmpc_mlp_rollout_grad_workspace_bytes(5, nx, nu, H) == gwb);
+            EXPECT(dmpc_mlp_rollout_grad_partials(5, H) == (H >= 1 ? dmpc_mlp_param_grad_partials(5) : 0));
+            const int rv = dmpc_mlp_rollout_grad(T, 5, nx, nu, H, act, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, ws, gwb, nullptr);
+            if (!sized || T <= 0) EXPECT(rv == DMPC_E_BADARG);
+            else if (!ok) EXPECT(rv == DMPC_E_UNSUPPORTED);
+            else EXPECT(rv >= 0);
+            if (ok && T > 0)      // grad_x is read at every T: d_x_init = grad_x[0] when T = 1
+              EXPECT(dmpc_mlp_rollout_grad(T, 5, nx, nu, H, 0, 1, p, p, p, p, p, p, nullptr, p, p, p, p, p, p, ws, gwb, nullptr) ==
+                     DMPC_E_BADARG);
+            if (ok && T > 1) {
+              EXPECT(dmpc_mlp_rollout_grad(T, 5, nx, nu, H, 0, 1, p, p, p, p, p, p, p, p, p, p, p, nullptr, nullptr, ws, gwb - 1,
+                                           nullptr) == DMPC_E_WORKSPACE);
+              EXPECT(dmpc_mlp_rollout_grad(T, 5, nx, nu, H, 0, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, nullptr, gwb, nullptr) ==
+                     DMPC_E_WORKSPACE);
+            }
           }
   // two hidden layers: n_hidden = DMPC_MLP_HIDDEN2(H1, H2); the rollout and the search take it, the weight gradient refuses it
   for (int H1 : {0, 1, 5, 128, 129})
@@ -232,6 +249,16 @@ int main() {
                    DMPC_E_WORKSPACE);
             EXPECT(dmpc_mlp2_param_grad(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, nullptr, g2, nullptr) == DMPC_E_WORKSPACE);
           }
+        }
+        // ... and dmpc_mlp_rollout_grad takes both codes
+        EXPECT(dmpc_mlp_rollout_grad_workspace_bytes(5, 16, 8, H) == g2);
+        const int rv2 = dmpc_mlp_rollout_grad(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, ws, g2, nullptr);
+        EXPECT(ok ? rv2 >= 0 : rv2 == DMPC_E_UNSUPPORTED);
+        if (ok && T > 1) {
+          EXPECT(dmpc_mlp_rollout_grad_partials(5, H) == dmpc_mlp2_param_grad_partials(5));
+          EXPECT(dmpc_mlp_rollout_grad(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, p, p, nullptr, nullptr, ws, g2 - 1, nullptr) ==
+                 DMPC_E_WORKSPACE);
+          EXPECT(dmpc_mlp_rollout_grad(T, 5, 16, 8, H, 3, 1, p, p, p, p, p, p, p, p, p, p, p, p, p, nullptr, g2, nullptr) == DMPC_E_WORKSPACE);
         }
         const float mlp2[4] = {(float)H, 3.f, 1.f, 0.f};
         if (T > 1) {
