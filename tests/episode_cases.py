@@ -55,21 +55,31 @@ def stage_cost(C0, c0, x, u):
     return 0.5 * np.einsum("bi,bij,bj->b", tau, np.asarray(C0, np.float64), tau) + (np.asarray(c0, np.float64) * tau).sum(axis=1)
 
 
+def oracle_lin_episode(bounds=None):
+    """-> dict(x [n+1,B,nx], u [n,B,nu], n_iter [n], warm [n,T,B,nu]) of the float64 episode; `bounds` = (lower, upper) [T,B,nu]
+    in place of the problem's own (`warm`: the plan every solve started from, zeros at the first)"""
+    return _lin_episode(None) if bounds is None else _run_lin_episode(dict(lin_problem(), lo=bounds[0], hi=bounds[1]))
+
+
 @functools.lru_cache(maxsize=None)
-def oracle_lin_episode():
-    """-> dict(x [n+1,B,nx], u [n,B,nu], n_iter [n]) of the float64 episode"""
-    k, P = LIN, lin_problem()
+def _lin_episode(_):
+    return _run_lin_episode(lin_problem())
+
+
+def _run_lin_episode(P):
+    k = LIN
     nx, nu, T = k["nx"], k["nu"], k["T"]
     cost, dyn = ompc.QuadCost(P["C"], P["c"]), ompc.LinDx(P["F"], P["f"])
     x, warm = P["x_init"], None
-    xs, us, iters = [x], [], []
+    xs, us, iters, warms = [x], [], [], []
     for _ in range(N_STEPS):
+        warms.append(np.zeros_like(P["lo"]) if warm is None else warm)
         _, u_plan, _, _, n_iter, *_ = obox.box_ddp(x, cost, dyn, T, P["lo"], P["hi"], nx, nu, u_init=warm, eps=EPS, max_iter=MAX_ITER,
                                                    batch_coupled=False, line_search_decay=LS_DECAY, max_line_search_iter=MAX_LS_ITER)
         x = lin_plant_step(P, x, u_plan[0])
         xs.append(x), us.append(u_plan[0]), iters.append(n_iter)
         warm = shift_plan(u_plan)
-    return dict(x=np.stack(xs), u=np.stack(us), n_iter=np.array(iters))
+    return dict(x=np.stack(xs), u=np.stack(us), n_iter=np.array(iters), warm=np.stack(warms))
 
 
 def mlp_packed(net):
