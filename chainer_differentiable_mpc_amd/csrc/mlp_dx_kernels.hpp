@@ -20,10 +20,8 @@
 //   mpc_forward_rec_mlp_kernel     MPCstep.forward_rec (mpc/mpc_step.py:175-286) with the network as the TRUE dynamics:
 //                                  the clamped closed-loop rollout and per-trajectory line search of
 //                                  mpc_generic_forward_kernel, the dynamics evaluated in place of F tau + f.
-//   mlp_param_grad_kernel,         the gradient of a loss of the rollout's f with respect to W1, b1, W2, b2 (depth one): per-wavefront
-//   mlp_param_grad_reduce_kernel   sums in registers, then a fixed-order reduction of the partials (at the end of this file).
-//                                  The same sweeps with the co-state carried, for a loss of the rolled states themselves, are
-//                                  siblings in mlp_rollout_grad_kernels.hpp; they store these partials for these reductions.
+// The reverse sweeps over the rollout - the gradients with respect to the weights - are built on these pieces in
+// mlp_grad_kernels.hpp.
 //
 // Layout.  Runtime dimensions (nx <= 16, nu <= 8), ONE wavefront per trajectory, four per workgroup.  The weights are
 // staged into LDS once per workgroup (mlp_stage) and shared by its wavefronts - the matrices in layer order, then the biases:
@@ -510,358 +508,6 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_kernel(con
   static_assert(DEPTH == 2, "the depth-one kernel is mpc_forward_rec_mlp_kernel<ACT>");
   extern __shared__ float lds[];
   mpc_forward_rec_mlp_body<ACT, DEPTH>(a, m, lds);
-}
-
-// The gradient of L(f) with respect to W1, b1, W2, b2 for f_t = next(x_t, u_t) - F_t [x_t;u_t] along the rolled states,
-// F_t a CONSTANT with the value of the live Jacobian (MlpDx.linearize; mpc/approximate.py:77-119).  With z_t = [x_t;u_t],
-// a_t = act(W1 z_t + b1), d_t = act'(W1 z_t + b1), g_t = dL/df_t, lam_{T-1} = 0, for t = T-2 .. 0:
-//     r     = g_t + lam_{t+1}
-//     delta = d_t * (W2^T r)
-//     dW2 += r a_t^T ;  db2 += r ;  dW1 += delta z_t^T ;  db1 += delta
-//     e     = d_t * (W2^T lam_{t+1}) ;  du_t = W1[:, nx:]^T e ;  lam_t = W1[:, :nx]^T e (+ lam_{t+1} when residual)
-// Every term of lam_t carries a factor lam_{t+1}, and lam_{T-1} = 0: lam_t = 0, e = 0 and du_t = 0 for every t, as exact
-// zeros in any arithmetic and for every activation - next's derivative through z_t and F_t's cancel at every step,
-// nothing is left to carry.
-// So r = g_t, the lines of e, du and lam are not evaluated, and d_x_init, d_u are stored as the zeros they are.
-//
-// One wavefront per trajectory as above; wavefront w of G serves trajectories w, w + G, ... in ascending order, t
-// descending, and keeps the sums for ITS hidden units (lane, lane + 64, ...) in registers - rows of dW1, columns of dW2,
-// db1; lanes < nx keep db2 - every array indexed by unrolled loops with wave-uniform guards, never by a runtime value.
-// It stores one partial [dW1 | db1 | dW2 | db2], laid out as the parameters are, at part + w * P.
-// mlp_param_grad_reduce_kernel adds the G partials per element in ascending order: no atomics, and a result that depends
-// on (T, B, nx, nu, H) and the data alone.
-constexpr int kMlpGradCap = 512;                             // partials at most: 21.5 MB at the largest model
-__host__ __device__ inline int mlp_grad_partials(int B) { return B < kMlpGradCap ? B : kMlpGradCap; }
-__host__ __device__ inline int mlp_grad_partial_floats(int nx, int nu, int H) { return H * (nx + nu) + H + nx * H + nx; }
-
-struct MlpGradArgs {
-  int T, B, G;
-  MlpModel m;
-  const float *x, *u, *grad_f;   // [T,B,nx] as the rollout stored them, [T,B,nu], [T-1,B,nx]
-  float *part;                   // [G][P]
-  float *d_x_init, *d_u;         // [B,nx], [T,B,nu], each or nullptr
-};
-
-template <int ACT>
-__global__ __launch_bounds__(64 * kMlpWaves) void mlp_param_grad_kernel(const MlpGradArgs a) {
-  extern __shared__ float lds[];
-  constexpr int UNITS = mlp_units(1);
-  const MlpLds<1> L = mlp_stage<1>(a.m, lds);
-  const int lane = threadIdx.x % 64;
-  const int w = blockIdx.x * kMlpWaves + threadIdx.x / 64;
-  if (w >= a.G) return;      // (after the only barrier)
-  const int nx = a.m.nx, nu = a.m.nu, ns = nx + nu, H = a.m.H[0];
-  const int T = a.T;
-  const size_t B = (size_t)a.B;
-  const MlpUnits<UNITS> U(lane, H);
-  float dW1[UNITS][kMlpMaxNx + kMlpMaxNu] = {}, dW2[UNITS][kMlpMaxNx] = {}, db1[UNITS] = {}, db2 = 0.f;
-
-  for (size_t b = w; b < B; b += a.G) {
-    if (a.d_x_init != nullptr && lane < nx) a.d_x_init[b * nx + lane] = 0.f;
-    if (a.d_u != nullptr && lane < nu)
-      for (int t = 0; t < T; ++t) a.d_u[((size_t)t * B + b) * nu + lane] = 0.f;
-    for (int t = T - 2; t >= 0; --t) {
-      const size_t tb = (size_t)t * B + b;
-      const float tau = lane < nx ? a.x[tb * nx + lane] : (lane < ns ? a.u[tb * nu + (lane - nx)] : 0.f);
-      const float r = lane < nx ? a.grad_f[tb * nx + lane] : 0.f;
-      float z[UNITS], act[UNITS], dact[UNITS];
-      mlp_layer_from_lanes(L.W[0], L.ld[0], L.b[0], U, ns, tau, z);
-#pragma unroll
-      for (int k = 0; k < UNITS; ++k) mlp_activate<ACT>(U.live(k), z[k], act[k], dact[k]);
-      db2 += r;
-      float s[UNITS] = {};                               // W2^T r at this lane's units
-#pragma unroll
-      for (int i = 0; i < kMlpMaxNx; ++i) {
-        if (i < nx) {
-          const float ri = lane_value(r, i);
-#pragma unroll
-          for (int k = 0; k < UNITS; ++k) {
-            if (k < U.n) {
-              const float w2 = L.W[1][i * L.ld[1] + U.row[k]];
-              s[k] = fmaf(U.has[k] ? w2 : 0.f, ri, s[k]);
-              dW2[k][i] = fmaf(ri, act[k], dW2[k][i]);
-            }
-          }
-        }
-      }
-      float delta[UNITS];
-#pragma unroll
-      for (int k = 0; k < UNITS; ++k) {
-        delta[k] = dact[k] * s[k];
-        db1[k] += delta[k];
-      }
-#pragma unroll
-      for (int j = 0; j < kMlpMaxNx + kMlpMaxNu; ++j) {
-        if (j < ns) {
-          const float tj = lane_value(tau, j);
-#pragma unroll
-          for (int k = 0; k < UNITS; ++k)
-            if (k < U.n) dW1[k][j] = fmaf(delta[k], tj, dW1[k][j]);
-        }
-      }
-    }
-  }
-
-  float *p = a.part + (size_t)w * mlp_grad_partial_floats(nx, nu, H);
-  float *pb1 = p + H * ns, *pW2 = pb1 + H, *pb2 = pW2 + nx * H;
-#pragma unroll
-  for (int k = 0; k < UNITS; ++k) {
-    const int h = lane + 64 * k;
-    if (h < H) {
-#pragma unroll
-      for (int j = 0; j < kMlpMaxNx + kMlpMaxNu; ++j)
-        if (j < ns) p[h * ns + j] = dW1[k][j];
-      pb1[h] = db1[k];
-#pragma unroll
-      for (int i = 0; i < kMlpMaxNx; ++i)
-        if (i < nx) pW2[i * H + h] = dW2[k][i];
-    }
-  }
-  if (lane < nx) pb2[lane] = db2;
-}
-
-struct MlpGradReduceArgs {
-  int G, nx, nu, n_hidden;
-  const float *part;               // [G][P]
-  float *dW1, *db1, *dW2, *db2;    // [H,ns], [H], [nx,H], [nx]
-};
-
-// one thread per parameter element; G = 0 stores zeros (T = 1: no dynamics step, no partials)
-__global__ __launch_bounds__(256) void mlp_param_grad_reduce_kernel(const MlpGradReduceArgs a) {
-  const int H = a.n_hidden, n1 = H * (a.nx + a.nu), n2 = a.nx * H;
-  const int P = mlp_grad_partial_floats(a.nx, a.nu, H);
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= P) return;
-  float s = 0.f;
-#pragma unroll 8
-  for (int w = 0; w < a.G; ++w) s += a.part[(size_t)w * P + e];
-  if (e < n1) a.dW1[e] = s;
-  else if (e < n1 + H) a.db1[e - n1] = s;
-  else if (e < n1 + H + n2) a.dW2[e - n1 - H] = s;
-  else a.db2[e - n1 - H - n2] = s;
-}
-
-// The same gradient with TWO hidden layers (include/dmpc_mlp_grad.h).  As above the co-state is exactly zero, r = g_t, and each
-// step adds, with tau = [x_t;u_t] and the forward pieces of MlpNet<2> (mlp_layer_from_lanes, mlp_layer_from_units, mlp_activate):
-//     dW3 += r a2^T ;  db3 += r ;  e2 = d2 * (W3^T r) ;  dW2 += e2 a1^T ;  db2 += e2 ;  e1 = d1 * (W2^T e2) ;  dW1 += e1 tau^T ;  db1 += e1
-//
-// One wavefront per trajectory, four per workgroup; workgroup g of G serves the trajectory groups g, g + G, ... in ascending
-// order (b = 4 group + slot), t descending.  Who keeps what:
-//     a wavefront, in the registers of the lane that owns the unit (lane, lane + 64):
-//         rows of dW1 and db1 (layer-1 units), columns of dW3 and db2 (layer-2 units), db3 (lanes < nx)   - 85 per lane
-//     the workgroup: dW2 [H2,H1], up to 16,384 sums - wavefront w keeps rows 32 w .. 32 w + 31, a lane columns lane and
-//         lane + 64 of them: 64 per lane.  Each step every wavefront publishes a1 and e2 of ITS trajectory (both complete to 128
-//         entries, exact zeros beyond the widths) into a double-buffered exchange behind the staged weights, and after ONE
-//         workgroup barrier every wavefront adds the four outer products into its rows: plain fmaf, slot ascending.
-// The barrier is workgroup-uniform: every wavefront runs the trip counts of its workgroup.  A slot without a trajectory (b >= B)
-// walks the clamped addresses of trajectory B - 1 and replaces every activation and derivative by 0, so all it adds are exact
-// zeros.  Two buffers suffice: a wavefront that writes buffer n & 1 at step n + 2 has passed barrier n + 1, behind which
-// nobody reads step n's.
-// At the end the four wavefronts' register sums are added in slot order 0, 1, 2, 3 in LDS (over the weights, which nobody reads
-// any more) and the workgroup stores ONE partial [dW1 | db1 | dW2 | dW3 | db2 | db3] - the order of the packed weights - at
-// part + g * P.  mlp2_param_grad_reduce_kernel adds the G partials per element in ascending order: no atomics, a result that
-// depends on (T, B, nx, nu, H1, H2) and the data alone.
-constexpr int kMlp2GradCap = 256;                            // partials at most: one resident workgroup per CU; 22.3 MB at the largest model
-constexpr int kMlp2GradRows = mlp_max_hidden(2) / kMlpWaves;          // rows of dW2 a wavefront keeps
-constexpr int kMlp2GradExchangeFloats = 2 * kMlpWaves * 2 * mlp_max_hidden(2);   // two buffers of [slot][a1 (128) | e2 (128)]
-__host__ __device__ inline int mlp2_grad_partials(int B) {
-  const int groups = B / kMlpWaves + (B % kMlpWaves != 0 ? 1 : 0);       // (no overflow at any B)
-  return groups < kMlp2GradCap ? groups : kMlp2GradCap;
-}
-__host__ __device__ inline int mlp2_grad_partial_floats(int nx, int nu, int H1, int H2) {
-  return H1 * (nx + nu) + H1 + H2 * H1 + nx * H2 + H2 + nx;
-}
-constexpr size_t mlp2_grad_lds_bytes(int nx, int nu, int H1, int H2) {
-  return mlp_lds_bytes(nx, nu, H1, H2, false) + kMlp2GradExchangeFloats * sizeof(float);
-}
-static_assert(mlp2_grad_lds_bytes(16, 8, 128, 128) == 96384 && mlp2_grad_lds_bytes(16, 8, 128, 128) <= kMlpLdsLimit, "weights + exchange");
-
-template <int ACT>
-__global__ __launch_bounds__(64 * kMlpWaves) void mlp2_param_grad_kernel(const MlpGradArgs a) {
-  extern __shared__ float lds[];
-  constexpr int UNITS = mlp_units(2), HMAX = mlp_max_hidden(2), ROWS = kMlp2GradRows;
-  static_assert(UNITS == 2 && ROWS == 32, "a lane owns two units of a layer and two columns of 32 rows of dW2");
-  const MlpLds<2> L = mlp_stage<2>(a.m, lds);
-  float *const ex = L.b[2] + a.m.nx;           // the exchange, behind the staged biases
-  const int lane = threadIdx.x % 64, wv = threadIdx.x / 64;
-  const int nx = a.m.nx, nu = a.m.nu, ns = nx + nu, H1 = a.m.H[0], H2 = a.m.H[1];
-  const int T = a.T;
-  const size_t B = (size_t)a.B;
-  const int groups = (a.B + kMlpWaves - 1) / kMlpWaves;
-  const MlpUnits<UNITS> U1(lane, H1), U2(lane, H2);
-  const int row0 = ROWS * wv;
-  float dW1[UNITS][kMlpMaxNx + kMlpMaxNu] = {}, db1[UNITS] = {}, dW3[UNITS][kMlpMaxNx] = {}, db2[UNITS] = {}, db3 = 0.f;
-  float dW2[ROWS][UNITS] = {};
-  int step = 0;
-
-  for (int grp = blockIdx.x; grp < groups; grp += a.G) {      // workgroup-uniform
-    const size_t b0 = (size_t)grp * kMlpWaves + wv;
-    const bool live = b0 < B;                                  // wave-uniform
-    const size_t b = live ? b0 : B - 1;
-    if (live) {
-      if (a.d_x_init != nullptr && lane < nx) a.d_x_init[b * nx + lane] = 0.f;
-      if (a.d_u != nullptr && lane < nu)
-        for (int t = 0; t < T; ++t) a.d_u[((size_t)t * B + b) * nu + lane] = 0.f;
-    }
-    for (int t = T - 2; t >= 0; --t, ++step) {
-      const size_t tb = (size_t)t * B + b;
-      const float tau = lane < nx ? a.x[tb * nx + lane] : (lane < ns ? a.u[tb * nu + (lane - nx)] : 0.f);
-      const float r = live && lane < nx ? a.grad_f[tb * nx + lane] : 0.f;
-      float z[UNITS], a1[UNITS], d1[UNITS], a2[UNITS], d2[UNITS];
-      mlp_layer_from_lanes(L.W[0], L.ld[0], L.b[0], U1, ns, tau, z);
-#pragma unroll
-      for (int k = 0; k < UNITS; ++k) mlp_activate<ACT>(live && U1.live(k), z[k], a1[k], d1[k]);
-      mlp_layer_from_units(L.W[1], L.ld[1], L.b[1], U2, H1, a1, z);
-#pragma unroll
-      for (int k = 0; k < UNITS; ++k) mlp_activate<ACT>(live && U2.live(k), z[k], a2[k], d2[k]);
-
-      db3 += r;
-      float s2[UNITS] = {};                              // W3^T r at this lane's layer-2 units
-#pragma unroll
-      for (int i = 0; i < kMlpMaxNx; ++i) {
-        if (i < nx) {
-          const float ri = lane_value(r, i);
-#pragma unroll
-          for (int k = 0; k < UNITS; ++k) {
-            if (k < U2.n) {
-              const float w3 = L.W[2][i * L.ld[2] + U2.row[k]];
-              s2[k] = fmaf(U2.has[k] ? w3 : 0.f, ri, s2[k]);
-              dW3[k][i] = fmaf(ri, a2[k], dW3[k][i]);
-            }
-          }
-        }
-      }
-      float e2[UNITS];
-#pragma unroll
-      for (int k = 0; k < UNITS; ++k) {
-        e2[k] = d2[k] * s2[k];
-        db2[k] += e2[k];
-      }
-
-      // publish a1 and e2 (zeros beyond the widths and in a slot without a trajectory), then the workgroup's one barrier
-      float *const exb = ex + (step & 1) * (kMlpWaves * 2 * HMAX);
-#pragma unroll
-      for (int k = 0; k < UNITS; ++k) {
-        exb[wv * 2 * HMAX + lane + 64 * k] = a1[k];
-        exb[wv * 2 * HMAX + HMAX + lane + 64 * k] = e2[k];
-      }
-      __syncthreads();
-
-      float s1[UNITS] = {};                              // W2^T e2 at this lane's layer-1 units: column reads of the staged W2
-#pragma unroll
-      for (int k2 = 0; k2 < UNITS; ++k2) {
-        const int left = H2 - 64 * k2, cnt = left < 64 ? left : 64;
-        for (int l = 0; l < cnt; ++l) {
-          const float eh = lane_value(e2[k2], l);
-#pragma unroll
-          for (int k = 0; k < UNITS; ++k) {
-            if (k < U1.n) {
-              const float w2 = L.W[1][(64 * k2 + l) * L.ld[1] + U1.row[k]];
-              s1[k] = fmaf(U1.has[k] ? w2 : 0.f, eh, s1[k]);
-            }
-          }
-        }
-      }
-      float e1[UNITS];
-#pragma unroll
-      for (int k = 0; k < UNITS; ++k) {
-        e1[k] = d1[k] * s1[k];
-        db1[k] += e1[k];
-      }
-#pragma unroll
-      for (int j = 0; j < kMlpMaxNx + kMlpMaxNu; ++j) {
-        if (j < ns) {
-          const float tj = lane_value(tau, j);
-#pragma unroll
-          for (int k = 0; k < UNITS; ++k)
-            if (k < U1.n) dW1[k][j] = fmaf(e1[k], tj, dW1[k][j]);
-        }
-      }
-
-      // this wavefront's rows of dW2: the four trajectories' e2[row] a1[column], slot ascending
-      float a1s[kMlpWaves][UNITS], e2s[kMlpWaves];
-#pragma unroll
-      for (int s = 0; s < kMlpWaves; ++s) {
-#pragma unroll
-        for (int k = 0; k < UNITS; ++k) a1s[s][k] = exb[s * 2 * HMAX + lane + 64 * k];
-        e2s[s] = exb[s * 2 * HMAX + HMAX + row0 + lane % ROWS];       // row row0 + l in lane l < 32
-      }
-#pragma unroll
-      for (int q = 0; q < ROWS; q += 8) {
-        if (row0 + q < H2) {                             // wave-uniform; rows beyond H2 inside the eight add exact zeros
-#pragma unroll
-          for (int rr = q; rr < q + 8; ++rr) {
-#pragma unroll
-            for (int s = 0; s < kMlpWaves; ++s) {
-              const float e = lane_value(e2s[s], rr);
-#pragma unroll
-              for (int k = 0; k < UNITS; ++k) dW2[rr][k] = fmaf(e, a1s[s][k], dW2[rr][k]);
-            }
-          }
-        }
-      }
-    }
-  }
-
-  // the workgroup's partial.  dW2 straight from its owners; the rest summed over the wavefronts in slot order, in LDS
-  const int n1 = H1 * ns, n2 = H2 * H1, n3 = nx * H2;
-  float *const p = a.part + (size_t)blockIdx.x * mlp2_grad_partial_floats(nx, nu, H1, H2);
-  float *const pW2 = p + n1 + H1;
-#pragma unroll
-  for (int rr = 0; rr < ROWS; ++rr) {
-#pragma unroll
-    for (int k = 0; k < UNITS; ++k) {
-      const int h2 = row0 + rr, h1 = lane + 64 * k;
-      if (h2 < H2 && h1 < H1) pW2[h2 * H1 + h1] = dW2[rr][k];
-    }
-  }
-  __syncthreads();                                       // nobody reads the weights or the exchange any more
-  float *const q1 = lds, *const qb1 = q1 + n1, *const q3 = qb1 + H1, *const qb2 = q3 + n3, *const qb3 = qb2 + H2;
-  for (int s = 0; s < kMlpWaves; ++s) {
-    if (wv == s) {
-      const bool first = s == 0;
-#pragma unroll
-      for (int k = 0; k < UNITS; ++k) {
-        const int h = lane + 64 * k;
-        if (h < H1) {
-#pragma unroll
-          for (int j = 0; j < kMlpMaxNx + kMlpMaxNu; ++j)
-            if (j < ns) q1[h * ns + j] = first ? dW1[k][j] : q1[h * ns + j] + dW1[k][j];
-          qb1[h] = first ? db1[k] : qb1[h] + db1[k];
-        }
-        if (h < H2) {
-#pragma unroll
-          for (int i = 0; i < kMlpMaxNx; ++i)
-            if (i < nx) q3[i * H2 + h] = first ? dW3[k][i] : q3[i * H2 + h] + dW3[k][i];
-          qb2[h] = first ? db2[k] : qb2[h] + db2[k];
-        }
-      }
-      if (lane < nx) qb3[lane] = first ? db3 : qb3[lane] + db3;
-    }
-    __syncthreads();
-  }
-  const int Q = n1 + H1 + n3 + H2 + nx;                  // the partial without dW2, which sits behind db1
-  for (int e = threadIdx.x; e < Q; e += 64 * kMlpWaves) p[e < n1 + H1 ? e : e + n2] = lds[e];
-}
-
-struct Mlp2GradReduceArgs {
-  int G, n1, nb1, n2, nb2;         // partials; elements of dW1, db1, [dW2 | dW3], [db2 | db3] - a partial in this order
-  const float *part;               // [G][P]
-  float *dW1, *db1, *dW2, *db2;    // [H1,ns], [H1], [H2*H1 | nx*H2], [H2 | nx]
-};
-
-// one thread per parameter element; G = 0 stores zeros (T = 1: no dynamics step, no partials)
-__global__ __launch_bounds__(256) void mlp2_param_grad_reduce_kernel(const Mlp2GradReduceArgs a) {
-  const int P = a.n1 + a.nb1 + a.n2 + a.nb2;
-  const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= P) return;
-  float s = 0.f;
-#pragma unroll 8
-  for (int g = 0; g < a.G; ++g) s += a.part[(size_t)g * P + e];
-  if (e < a.n1) a.dW1[e] = s;
-  else if (e < a.n1 + a.nb1) a.db1[e - a.n1] = s;
-  else if (e < a.n1 + a.nb1 + a.n2) a.dW2[e - a.n1 - a.nb1] = s;
-  else a.db2[e - a.n1 - a.nb1 - a.n2] = s;
 }
 
 }  // namespace dmpc

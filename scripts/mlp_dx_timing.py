@@ -13,6 +13,14 @@ and autograd through it: the baseline) on equal weights in the same run.
 `--chain` times the iLQR loop itself: the host loop (`MlpDx(device_loop=False)`, the default route) against `dmpc_box_ddp`'s
 chain with the network inside it (`device_loop=True`: `search_linearizes` 0 and 1 launched directly, and the hipGraph replay).
 
+`--sweeps LIB[,LIB...]` times the gradient sweeps themselves (csrc/mlp_grad_kernels.hpp): `dmpc_mlp_param_grad`,
+`dmpc_mlp2_param_grad` and `dmpc_mlp_rollout_grad` called directly through the C ABI of each named library (`tree`: the one in
+the tree) - device events around a burst of back-to-back calls on one stream, long enough that the kernel is resolved, the
+median and the range over `--iters` bursts, in ms per call.  The libraries take turns, the whole round twice, so a parent and
+a head library are measured alternately in one run; with two libraries the two-run rule of DESIGN.md 3.4 is applied to the
+second against the first (its worse run no further above the first's mean than the first's two runs are apart).  Sizes:
+`--batch`, `--horizon` with (3,1) H 32, (8,2) H 64, (8,2) H (64,64) and each depth's largest model.
+
 `--activation` picks the network (tanh, relu, silu, softplus; default tanh, whose output lines are what they were before
 the flag existed - another activation adds an "activation" key).
 
@@ -20,7 +28,7 @@ the flag existed - another activation adds an "activation" key).
 the pair).  The run fails if the device route is not faster than the plain callable measured beside it; with `--grad`, if
 solve + backward on the device route is slower than on the live route of the same run.
 
-    python scripts/mlp_dx_timing.py [--grad | --chain] [--iters 20] [--warmup 3] [--cases 3x1x32,8x2x64] [--batch 128] [--horizon 20]
+    python scripts/mlp_dx_timing.py [--grad | --chain | --sweeps parent.so,tree] [--iters 20] [--warmup 3] [--cases 3x1x32,8x2x64] [--batch 128] [--horizon 20]
                                     [--activation tanh] [--hidden2 H2] [--json out]"""
 import argparse
 import json
@@ -179,9 +187,84 @@ def run_grad_case(nx, nu, H, B, T, iters, warmup, activation="tanh"):
     return out
 
 
+SWEEP_CASES = ((3, 1, (32,)), (8, 2, (64,)), (8, 2, (64, 64)), (16, 8, (256,)), (16, 8, (128, 128)))
+
+
+def run_sweeps(libs, B, T, iters, burst=20):
+    """-> one dict per (model, entry point): per library its two runs' (median, min, max) ms per call, and the rule"""
+    import numpy as np
+
+    from chainer_differentiable_mpc_amd import _lib
+    loaded = [(name, _lib.load() if name == "tree" else _lib.load(name)) for name in libs]
+    ptr = lambda t: t.data_ptr()   # noqa: E731
+    res = []
+    for nx, nu, hidden in SWEEP_CASES:
+        m = MlpDx(nx, nu, hidden[0] if len(hidden) == 1 else hidden, seed=0).cuda()
+        w = [p.detach().contiguous() for p in m._weights()]
+        if len(hidden) == 2:          # the C ABI's [W2 | W3], [b2 | b3]
+            w = [w[0], w[1], torch.cat((w[2].reshape(-1), w[4].reshape(-1))), torch.cat((w[3], w[5]))]
+        code = hidden[0] if len(hidden) == 1 else _lib.mlp_hidden2(*hidden)
+        rng = np.random.RandomState(1)
+        dev = lambda a: torch.as_tensor(a, dtype=torch.float32, device="cuda")   # noqa: E731
+        x_init, u, g = dev(rng.randn(B, nx)), dev(0.5 * rng.randn(T, B, nu)), dev(rng.randn(T, B, nx))
+        x = torch.zeros(T, B, nx, device="cuda")
+        head = [T, B, nx, nu, code, 0, 1] + [ptr(a) for a in w]
+        assert loaded[0][1].dmpc_mlp_rollout_linearize(*head, ptr(x_init), ptr(u), ptr(x), None, None, None) == 0
+        outs = [torch.zeros_like(a) for a in w] + [torch.zeros(B, nx, device="cuda"), torch.zeros(T, B, nu, device="cuda")]
+        weight_grad = "dmpc_mlp_param_grad" if len(hidden) == 1 else "dmpc_mlp2_param_grad"
+        for entry in (weight_grad, "dmpc_mlp_rollout_grad"):
+            row = dict(leg="sweeps", nx=nx, nu=nu, n_hidden=list(hidden), B=B, T=T, entry=entry, burst=burst, runs={n: [] for n, _ in loaded})
+            for _ in range(2):
+                for name, lib in loaded:
+                    need = getattr(lib, entry + "_workspace_bytes")(B, nx, nu, code)
+                    ws = torch.zeros(need, dtype=torch.uint8, device="cuda")
+                    args = head + [ptr(x), ptr(u), ptr(g)] + [ptr(o) for o in outs] + [ptr(ws), need, None]
+
+                    def calls():
+                        for _ in range(burst):
+                            assert getattr(lib, entry)(*args) == 0
+                    for _ in range(3):
+                        calls()
+                    torch.cuda.synchronize()
+                    ts = []
+                    for _ in range(iters):
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record()
+                        calls()
+                        b.record()
+                        b.synchronize()
+                        ts.append(a.elapsed_time(b) / burst)
+                    ts.sort()
+                    row["runs"][name].append((ts[len(ts) // 2], ts[0], ts[-1]))
+            if len(loaded) == 2:
+                first, second = ([r[0] for r in row["runs"][n]] for n, _ in loaded)
+                row["above_first_mean"] = max(second) - sum(first) / 2
+                row["first_apart"] = abs(first[0] - first[1])
+                row["inside_rule"] = row["above_first_mean"] <= row["first_apart"]
+            res.append(row)
+    return res
+
+
+def print_sweeps_table(res):
+    """the rows once more as a table: per library the medians of its two runs; with two libraries the rule's columns"""
+    names = list(res[0]["runs"])
+    print("# libraries, in column order: " + ", ".join("%d = %s" % (i + 1, n) for i, n in enumerate(names)))
+    rule = "  %8s %7s  rule" % ("excess", "spread") if len(names) == 2 else ""
+    print("%-18s %-22s " % ("model", "entry") + " ".join("%8s %8s" % ("%d a" % (i + 1), "%d b" % (i + 1)) for i in range(len(names))) + rule)
+    for r in res:
+        line = "%-18s %-22s " % ("(%d,%d) H=%s" % (r["nx"], r["nu"], ",".join(str(h) for h in r["n_hidden"])), r["entry"])
+        line += " ".join("%8.4f %8.4f" % (r["runs"][n][0][0], r["runs"][n][1][0]) for n in names)
+        if len(names) == 2:
+            line += "  %+8.4f %7.4f  %s" % (r["above_first_mean"], r["first_apart"], "ok" if r["inside_rule"] else "ABOVE")
+        print(line)
+    if len(names) == 2:
+        print("rows above the rule: %s" % ([(r["n_hidden"], r["entry"]) for r in res if not r["inside_rule"]] or "none"), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grad", action="store_true")
+    ap.add_argument("--sweeps", default=None, help="libraries whose gradient entry points are timed in turn: paths, or `tree`")
     ap.add_argument("--chain", action="store_true")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -193,7 +276,12 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     res = []
-    for c in a.cases.split(","):
+    if a.sweeps:
+        res = run_sweeps(a.sweeps.split(","), a.batch, a.horizon, max(a.iters, 20))
+        for r in res:
+            print(json.dumps(r), flush=True)
+        print_sweeps_table(res)
+    for c in ([] if a.sweeps else a.cases.split(",")):
         nx, nu, H = (int(v) for v in c.split("x"))
         if a.hidden2 > 0:
             H = (H, a.hidden2)
