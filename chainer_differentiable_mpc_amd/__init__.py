@@ -21,6 +21,7 @@ from .box_ddp import BoxDDP  # noqa: F401
 from .mpc_net import MpcNet_cost, MpcNet_dx  # noqa: F401
 from .pendulum import PendulumDx  # noqa: F401
 from .mlp_dx import MlpDx  # noqa: F401
+from .mlp_cost import MlpCost  # noqa: F401
 from .closed_loop import ClosedLoop, EpisodeOut, plant_step, shift_plan  # noqa: F401
 from .il_env import IL_Env, Pendulum_Net_cost_logit  # noqa: F401
 from .pendulum_net import (OBSERVATION_MATRIX, Pendulum_Net_cost_lower_triangle,  # noqa: F401

@@ -1,5 +1,5 @@
-"""ctypes binding of libdmpc_hip.so (the C-ABI in include/dmpc.h, include/dmpc_mlp_grad.h, include/dmpc_episode.h and
-include/dmpc_mlp_rollout_grad.h).
+"""ctypes binding of libdmpc_hip.so (the C-ABI in include/dmpc.h, include/dmpc_mlp_grad.h, include/dmpc_episode.h,
+include/dmpc_mlp_rollout_grad.h and include/dmpc_mlp_cost.h).
 
 PyTorch is plumbing here: it owns device memory and the HIP stream; every solver call below is
 one C function taking raw device pointers.  There is NO CPU fallback: if the shared library is
@@ -114,6 +114,15 @@ ROLLOUT_GRAD_SIGNATURES = {
     "dmpc_mlp_rollout_grad": (_c_i, [_c_i] * 7 + [_c_f] * 13 + [_c_f, _c_sz, _c_f]),
 }
 
+# include/dmpc_mlp_cost.h one to one: the learned stage cost (MlpCost), in the same library
+MLP_COST_SIGNATURES = {
+    "dmpc_mlp_cost_supported": (_c_i, [_c_i] * 4),
+    "dmpc_mlp_cost_approx": (_c_i, [_c_i] * 6 + [_c_f] * 10 + [_c_f]),
+    "dmpc_mpc_forward_rec_mlp_cost": (_c_i, [_c_i] * 6 + [_c_f] * 13 + [ctypes.c_float, _c_i] + [_c_f] * 10),
+    "dmpc_mlp_cost_param_grad_workspace_bytes": (_c_sz, [_c_i] * 5),
+    "dmpc_mlp_cost_param_grad": (_c_i, [_c_i] * 6 + [_c_f] * 12 + [_c_f, _c_sz, _c_f]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -136,7 +145,7 @@ def load(path=None):
         lib = ctypes.CDLL(p)
         partial = os.environ.get("DMPC_LIB_PARTIAL") == "1" and (path is not None or "DMPC_LIB" in os.environ)
         for name, (res, args) in (list(SIGNATURES.items()) + list(GRAD_SIGNATURES.items()) + list(EPISODE_SIGNATURES.items())
-                                   + list(ROLLOUT_GRAD_SIGNATURES.items())):
+                                   + list(ROLLOUT_GRAD_SIGNATURES.items()) + list(MLP_COST_SIGNATURES.items())):
             if partial and not hasattr(lib, name):   # experiment builds of ONE translation unit (scripts/knob_variants.sh)
                 continue
             fn = getattr(lib, name)      # AttributeError if the .so lacks a declared symbol

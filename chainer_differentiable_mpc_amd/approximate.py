@@ -47,8 +47,11 @@ def approximate_cost(x, u, Cf):
     """second-order Taylor model of a cost tau -> [B]: (hessians [T,B,ns,ns], grads - H tau [T,B,ns], costs [T,B])
     (approximate.py:18-54).  As in the reference (chainer.grad with enable_double_backprop for the first derivative
     only) the Hessians are constants, while `grads - H tau` and `costs` stay differentiable - MPCstep's `dc` reaches
-    the parameters of a learnable non-quadratic cost."""
+    the parameters of a learnable non-quadratic cost.  A cost may provide the model itself (`MlpCost`: one launch): it is
+    asked through `approx_ok(x, u)` and answers through `approximate(x, u)`."""
     assert x.shape[0] == u.shape[0] and x.shape[1] == u.shape[1]
+    if hasattr(Cf, "approx_ok") and Cf.approx_ok(x, u):
+        return Cf.approximate(x, u)
     T = x.shape[0]
     ambient = torch.is_grad_enabled()
     tau = torch.cat((x, u), dim=2)

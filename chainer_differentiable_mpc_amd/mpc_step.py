@@ -89,6 +89,12 @@ def _is_device_mlp(dyn, nx, nu):
     return isinstance(dyn, MlpDx) and (dyn.n_state, dyn.n_ctrl) == (nx, nu) and dyn.supported()
 
 
+def _is_device_mlp_cost(cost, nx, nu, device):
+    """MlpCost with the step's dimensions, of a size the kernels serve, for a step on the GPU"""
+    from .mlp_cost import MlpCost
+    return isinstance(cost, MlpCost) and (cost.n_state, cost.n_ctrl) == (nx, nu) and device.type == "cuda" and cost.supported()
+
+
 def du_norm(u_old, u_new, scrambled=True):
     du = u_old - u_new
     T, B, nu = du.shape
@@ -347,9 +353,18 @@ class MPCstep:
         quad, p = isinstance(true_cost, QuadCost), _lib.ptr
         # the dynamics a kernel's line search evaluates itself (mpc_step.py:237-240): its entry point, what that takes in
         # front of the gains and what behind the cost
+        if quad:
+            Ct, ct = _lib.f32c(_as_tensor(true_cost.C), d), _lib.f32c(_as_tensor(true_cost.c), d)
+            cost_args = (p(Ct), p(ct))
         if quad and isinstance(true_dynamics, LinDx):
             Ft, ft = _lib.f32c(_as_tensor(true_dynamics.F), d), _lib.f32c(_as_tensor(true_dynamics.f), d)
             entry, head, dyn = "dmpc_mpc_forward_rec", (T, B, nx, nu), (p(Ft), p(ft))
+        elif isinstance(true_dynamics, LinDx) and _is_device_mlp_cost(true_cost, nx, nu, d):
+            # a learned stage cost, its weights as device pointers, in place of C_true, c_true (true_cost has no C)
+            Ft, ft = _lib.f32c(_as_tensor(true_dynamics.F), d), _lib.f32c(_as_tensor(true_dynamics.f), d)
+            weights = true_cost.device_weights(d)
+            entry, dyn, cost_args = "dmpc_mpc_forward_rec_mlp_cost", (p(Ft), p(ft)), ()
+            head = (T, B, nx, nu, true_cost.n_hidden, true_cost.act_code) + tuple(p(w) for w in weights)
         elif quad and _is_simple_pendulum(true_dynamics) and (nx, nu) == (3, 1):     # env_dx/pendulum.py
             g_, m_, l_ = (float(v) for v in true_dynamics.params.detach().cpu().tolist())
             entry, head = "dmpc_mpc_forward_rec_pendulum", (T, B)
@@ -363,7 +378,6 @@ class MPCstep:
             entry = None
         if entry is not None:
             lib = _lib.load()
-            Ct, ct = _lib.f32c(_as_tensor(true_cost.C), d), _lib.f32c(_as_tensor(true_cost.c), d)
             f32 = dict(dtype=torch.float32, device=d)
             x, u, u1 = torch.empty((T, B, nx), **f32), torch.empty((T, B, nu), **f32), torch.empty((T, B, nu), **f32)
             costs, old, alphas = torch.empty((B,), **f32), torch.empty((B,), **f32), torch.empty((B,), **f32)
@@ -371,7 +385,7 @@ class MPCstep:
             nls = torch.empty((B,), dtype=torch.int32, device=d)
             info = torch.zeros(B, dtype=torch.int32, device=d)
             with _lib.guard(d):
-                rc = getattr(lib, entry)(*head, p(Kd), p(kd), p(self._u), p(self._xs), p(self._lo), p(self._hi), p(Ct), p(ct),
+                rc = getattr(lib, entry)(*head, p(Kd), p(kd), p(self._u), p(self._xs), p(self._lo), p(self._hi), *cost_args,
                                          *dyn, float(ls_decay), int(max_ls_iter), p(x), p(u), p(costs), p(old), p(alphas),
                                          p(objs), p(u1), p(nls), p(info), _lib.stream_ptr(d))
             _lib.check(rc, entry)
@@ -395,6 +409,9 @@ class MPCstep:
             if isinstance(true_cost, QuadCost):
                 return get_cost(T, u, QuadCost(_lib.f32c(_as_tensor(true_cost.C), self._dev),
                                                _lib.f32c(_as_tensor(true_cost.c), self._dev)), x=x), None
+            if hasattr(true_cost, "stage_costs") and true_cost.approx_ok(x, u):
+                per = true_cost.stage_costs(x, u)       # one launch per pass instead of a Python call per timestep
+                return per.sum(dim=0), per
             tau = torch.cat((x, u), dim=2)
             per = torch.stack([true_cost(tau[t]) for t in range(T)], dim=0)
             return per.sum(dim=0), per

@@ -10,6 +10,7 @@
 #include "dmpc_mlp_grad.h"
 #include "dmpc_episode.h"
 #include "dmpc_mlp_rollout_grad.h"
+#include "dmpc_mlp_cost.h"
 
 static int checks = 0, bad = 0;
 #define EXPECT(cond)                                                   \
@@ -313,6 +314,42 @@ int main() {
     for (const float *bad_params : {frac, neg, res})
       EXPECT(episode(2, 4, 2, 3, 1, p, 0, nullptr, p, nullptr, 2, bad_params, ws, 0) == DMPC_E_BADARG);
   }
+  // the learned stage cost (include/dmpc_mlp_cost.h): the limits, every argument check, the workspace arithmetic, the host path
+  for (auto &s : shapes)
+    for (int H : {0, 1, 7, 64, 65, 256, 257})
+      for (int act : {0, 1, 2, 3, 4, 5}) {
+        const int nx = s[0], nu = s[1], ns = nx + nu;
+        const bool ok = nx <= 16 && nu <= 8 && H >= 1 && H <= 256 && act != 1 && act != 5;
+        const int refused = H < 1 ? DMPC_E_BADARG : DMPC_E_UNSUPPORTED;
+        EXPECT(dmpc_mlp_cost_supported(nx, nu, H, act) == (ok ? 1 : 0));
+        for (int T : {1, 2, 20})
+          for (int B : {1, 5, 4096}) {
+            const size_t gb = dmpc_mlp_cost_param_grad_workspace_bytes(T, B, nx, nu, H);
+            const long long pts = (long long)T * B;
+            if (nx <= 16 && nu <= 8 && H >= 1 && H <= 256)
+              EXPECT(gb == (size_t)(pts < 256 ? pts : 256) * (ns * ns + ns + H * ns + 2 * H) * sizeof(float));
+            else
+              EXPECT(gb == 0);
+            const int ra = dmpc_mlp_cost_approx(T, B, nx, nu, H, act, p, p, p, p, p, p, p, p, p, p, nullptr);
+            const int rv = dmpc_mlp_cost_approx(T, B, nx, nu, H, act, p, p, p, p, p, p, p, nullptr, nullptr, p, nullptr);
+            const int rs = dmpc_mpc_forward_rec_mlp_cost(T, B, nx, nu, H, act, p, p, p, p, p, p, p, p, p, p, p, T > 1 ? p : nullptr, nullptr,
+                                                         0.2f, 10, p, p, p, nullptr, p, nullptr, nullptr, pi, nullptr, nullptr);
+            const int rg = dmpc_mlp_cost_param_grad(T, B, nx, nu, H, act, p, p, p, p, p, p, nullptr, p, p, p, p, p, ws, gb, nullptr);
+            for (int r : {ra, rv, rs, rg}) EXPECT(ok ? r >= 0 : r == refused);      // (launches fail: no device)
+            if (ok) {
+              EXPECT(dmpc_mlp_cost_param_grad(T, B, nx, nu, H, act, p, p, p, p, p, p, p, p, p, p, p, p, ws, gb - 1, nullptr) == DMPC_E_WORKSPACE);
+              EXPECT(dmpc_mlp_cost_param_grad(T, B, nx, nu, H, act, p, p, p, p, p, p, p, p, p, p, p, p, nullptr, gb, nullptr) == DMPC_E_WORKSPACE);
+              EXPECT(dmpc_mlp_cost_param_grad(T, B, nx, nu, H, act, p, p, p, p, p, nullptr, nullptr, p, p, p, p, p, ws, gb, nullptr) == DMPC_E_BADARG);
+              EXPECT(dmpc_mlp_cost_approx(T, B, nx, nu, H, act, p, p, p, p, p, p, p, p, nullptr, p, nullptr) == DMPC_E_BADARG);
+              EXPECT(dmpc_mlp_cost_approx(T, B, nx, nu, H, act, p, p, p, p, p, p, p, nullptr, nullptr, nullptr, nullptr) == DMPC_E_BADARG);
+              if (T > 1)
+                EXPECT(dmpc_mpc_forward_rec_mlp_cost(T, B, nx, nu, H, act, p, p, p, p, p, p, p, p, p, p, p, nullptr, nullptr, 0.2f, 10, p, p, p,
+                                                     nullptr, p, nullptr, nullptr, pi, nullptr, nullptr) == DMPC_E_BADARG);
+            }
+          }
+      }
+  EXPECT(dmpc_mlp_cost_approx(1 << 12, 1 << 12, 16, 8, 256, 4, p, p, p, p, p, p, p, p, p, p, nullptr) == DMPC_E_UNSUPPORTED);   // T B ns^2 >= 2^31
+  EXPECT(dmpc_mlp_cost_param_grad_workspace_bytes(0, 4, 3, 1, 5) == 0 && dmpc_mlp_cost_param_grad_workspace_bytes(4, 0, 3, 1, 5) == 0);
   EXPECT(dmpc_mlp_param_grad_partials(0) == 0 && dmpc_mlp_param_grad_partials(1 << 30) == dmpc_mlp_param_grad_partials(1 << 20));
   EXPECT(dmpc_lqr_shared_workspace_bytes(0, 1, 1, 1) == 0 && dmpc_lqr_shared_saved_bytes(0, 1, 1) == 0);
   EXPECT(dmpc_lqr_kernel_family(0, 3) == DMPC_E_UNSUPPORTED);
