@@ -121,6 +121,10 @@ MLP_COST_SIGNATURES = {
     "dmpc_mpc_forward_rec_mlp_cost": (_c_i, [_c_i] * 6 + [_c_f] * 13 + [ctypes.c_float, _c_i] + [_c_f] * 10),
     "dmpc_mlp_cost_param_grad_workspace_bytes": (_c_sz, [_c_i] * 5),
     "dmpc_mlp_cost_param_grad": (_c_i, [_c_i] * 6 + [_c_f] * 12 + [_c_f, _c_sz, _c_f]),
+    "dmpc_box_ddp_mlp_cost_workspace_bytes": (_c_sz, [_c_i] * 4),
+    "dmpc_box_ddp_mlp_cost": (_c_i, [_c_i] * 4 + [_c_f] * 2 + [_c_i] * 3 + [_c_f] * 2 + [_c_i, _c_f] + [_c_f] * 3 +
+                              [ctypes.c_float, _c_i, ctypes.c_float, _c_i, ctypes.c_float, _c_i, _c_i, _c_i, _c_i] +
+                              [_c_f] * 7 + [_c_sz, _c_f, _c_f]),
 }
 
 _lib = None

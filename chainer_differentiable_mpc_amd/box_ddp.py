@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from .approximate import approximate_cost, linearize_dynamics
 from .lqr_recursion import _as_tensor, _device_of, _workspace
+from .mlp_cost import MlpCost
 from .mlp_dx import MlpDx
 from .mpc_step import MPCstep, _MPCstepTiledDxFn, _MPCstepTiledFn, _is_simple_pendulum
 from .util import LinDx, QuadCost, TiledLinDx, TiledQuadCost, get_cost, get_traj
@@ -58,8 +59,9 @@ class BoxDDP(torch.nn.Module):
         self.exit_unconverged = exit_unconverged
         self.update_dynamics = update_dynamics
         self.quiet = quiet          # suppress the reference's "Converged" / "Not improved lim" prints
-        # QuadCost with a LinDx, the built-in pendulum or an `MlpDx(device_loop=True)`: the whole loop is one chain of launches
-        # with the stop tests on the device (`dmpc_box_ddp`); False keeps the host loop over MPCstep objects
+        # QuadCost with a LinDx, the built-in pendulum or an `MlpDx(device_loop=True)`, or an `MlpCost(device_loop=True)` with a
+        # LinDx: the whole loop is one chain of launches with the stop tests on the device (`dmpc_box_ddp`,
+        # `dmpc_box_ddp_mlp_cost`); False keeps the host loop over MPCstep objects
         self.device_loop = device_loop
         # PNQP termination inside every MPC step: per trajectory (default; shard-invariant) or the reference's
         # batch-global tests (pnqp.py:139-144,172,187; the batch must fit one cooperative launch).  The outer
@@ -187,11 +189,25 @@ class BoxDDP(torch.nn.Module):
         with torch.no_grad():
             return dynamics.fused_ok(x_init, u)
 
+    def _cost_chain_ok(self, cost, dynamics, x_init):
+        """an `MlpCost` the chain of `dmpc_box_ddp_mlp_cost` serves: asked for, a supported size that is the solver's, a `LinDx`
+        with a dense F, T >= 2, GPU tensors, no batch-coupled termination"""
+        if not (isinstance(cost, MlpCost) and cost.device_loop and isinstance(dynamics, LinDx)) or self.batch_coupled or self.T < 2:
+            return False
+        if (cost.n_state, cost.n_ctrl) != (self.n_state, self.n_ctrl) or not cost.supported():
+            return False
+        F = dynamics.F
+        return isinstance(x_init, torch.Tensor) and x_init.is_cuda and isinstance(F, torch.Tensor) and F.is_cuda and \
+            cost.Q.is_cuda and F.dim() == 4
+
     def _device_loop(self, x_init, cost, dynamics, u, lo, hi):
         """box_ddp.py:123-230 behind one C call; returns (best, last full_du_norm) or None when the problem is not
         of the supported kind (then the host loop runs)."""
         T, B, nx, nu = self.T, self.n_batch, self.n_state, self.n_ctrl
         ns = nx + nu
+        net = isinstance(cost, MlpCost)      # the learned cost inside the chain (dmpc_box_ddp_mlp_cost); forward() has asked _cost_chain_ok
+        if net and not isinstance(dynamics, LinDx):
+            return None
         if isinstance(dynamics, LinDx):
             kind, params, Fd, fd = 0, None, dynamics.F, dynamics.f
         elif _is_simple_pendulum(dynamics) and dynamics.fused_ok(x_init, u) and (nx, nu) == (3, 1):
@@ -212,13 +228,17 @@ class BoxDDP(torch.nn.Module):
         if not torch.cuda.is_current_stream_capturing():
             for other in list(_UNRESOLVED):       # earlier solves whose read-back was deferred: their asserts come now
                 other._resolve()
-        d = _device_of(x_init, cost.C, u)
+        d = _device_of(x_init, cost.Q if net else cost.C, u)
         x0 = _lib.f32c(x_init.detach(), d)
-        C, c = _lib.f32c(_as_tensor(cost.C).detach(), d), _lib.f32c(_as_tensor(cost.c).detach(), d)
+        C = None if net else _lib.f32c(_as_tensor(cost.C).detach(), d)
+        c = None if net else _lib.f32c(_as_tensor(cost.c).detach(), d)
         F = None if Fd is None else _lib.f32c(_as_tensor(Fd).detach(), d)
         f = None if fd is None else _lib.f32c(_as_tensor(fd).detach(), d)
-        if list(C.shape) != [T, B, ns, ns] or list(c.shape) != [T, B, ns]:
+        if not net and (list(C.shape) != [T, B, ns, ns] or list(c.shape) != [T, B, ns]):
             return None
+        # the cost's weights as one packed buffer, refilled here on EVERY call (one launch; the same address each time) - also
+        # the call that replays a recording, which reads the same buffer.  The search stores the next Taylor model (mode 1).
+        packed, mode = (cost.packed_weights(d), 1) if net else (None, 0)
         if kind == 2:
             F = dynamics.packed_weights(d)       # (one launch; the same address on every call)
         elif F is not None and (F.shape[0] not in (T - 1, T) or list(F.shape[1:]) != [B, nx, ns]):
@@ -229,7 +249,7 @@ class BoxDDP(torch.nn.Module):
         # one float and one int32 allocation per solve; the input asserts of MPCstep (mpc_step.py:133-138) and the
         # reductions over info / full_du_norm come back in state[4:8] with the loop state (box_ddp_summary_kernel)
         n_x, n_u = T * B * nx, T * B * nu
-        need = lib.dmpc_box_ddp_workspace_bytes(T, B, nx, nu)
+        need = (lib.dmpc_box_ddp_mlp_cost_workspace_bytes if net else lib.dmpc_box_ddp_workspace_bytes)(T, B, nx, nu)
         scalars = (float(self.eps), int(self.not_improved_lim), float(self.ls_decay), int(self.max_ls_iter),
                    float(self.best_cost_eps), int(self.max_iter), 1 if self.batch_coupled else 0)
 
@@ -244,6 +264,14 @@ class BoxDDP(torch.nn.Module):
         def launch(out, ints, ws):
             bx, bu = out[:n_x], out[n_x:n_x + n_u]
             tail = out[n_x + n_u:]
+            if net:
+                with _lib.guard(d):
+                    return lib.dmpc_box_ddp_mlp_cost(T, B, nx, nu, _lib.ptr(x0), _lib.ptr(packed), cost.n_hidden, cost.act_code, mode,
+                                                     _lib.ptr(F), _lib.ptr(f), kind, None, _lib.ptr(u0), _lib.ptr(lo_), _lib.ptr(hi_),
+                                                     scalars[0], scalars[1], scalars[2], scalars[3], scalars[4], scalars[5], 20, 1,
+                                                     scalars[6], _lib.ptr(bx), _lib.ptr(bu), _lib.ptr(tail[:B]),
+                                                     _lib.ptr(tail[B:2 * B]), _lib.ptr(tail[2 * B:]), _lib.ptr(ints[B:]),
+                                                     _lib.ptr(ws), need, _lib.ptr(ints[:B]), _lib.stream_ptr(d))
             with _lib.guard(d):
                 return lib.dmpc_box_ddp(T, B, nx, nu, _lib.ptr(x0), _lib.ptr(C), _lib.ptr(c), _lib.ptr(F), _lib.ptr(f), kind,
                                         None if params is None else ctypes.cast(params, ctypes.c_void_p), _lib.ptr(u0),
@@ -264,6 +292,8 @@ class BoxDDP(torch.nn.Module):
             # (batch_coupled: its grid barriers need cooperative launches, which a stream capture does not take)
             key = (d, _lib.stream_ptr(d), T, B, nx, nu, kind, None if params is None else tuple(params), scalars) + tuple(
                 None if t is None else (t.data_ptr(), tuple(t.shape)) for t in (x0, C, c, F, f, u0, lo_, hi_))
+            if net:
+                key += (packed.data_ptr(), cost.n_hidden, cost.act_code, mode)
         entry = self._graphs.get(key) if key is not None else None
         rc = 0
         host_state = None
@@ -318,7 +348,7 @@ class BoxDDP(torch.nn.Module):
         info, state = ints[:B], ints[B:]
         if rc == _lib.E_UNSUPPORTED:
             return None
-        _lib.check(rc, "dmpc_box_ddp")
+        _lib.check(rc, "dmpc_box_ddp_mlp_cost" if net else "dmpc_box_ddp")
         self.__dict__["_loop_flag"] = state[7:8]              # device int: some trajectory's best full_du_norm is above eps (:263)
         self.__dict__["_warn_unconverged"] = False
         if capturing:
@@ -335,8 +365,8 @@ class BoxDDP(torch.nn.Module):
                 self._resolve()                   # the one synchronisation of the loop
         dev, dt = x_init.device, x_init.dtype
         self.__dict__["_fast"] = None
-        # (never for the network: _replay does not come through here, and a replay must follow a refill of the packed weights)
-        if kind != 2 and entry is not None and entry[0] is not None and dt == torch.float32 and dev == d and x0 is not None and \
+        # (never for a network: _replay does not come through here, and a replay must follow a refill of the packed weights)
+        if kind != 2 and not net and entry is not None and entry[0] is not None and dt == torch.float32 and dev == d and x0 is not None and \
                 x0.data_ptr() == x_init.data_ptr() and C.data_ptr() == cost.C.data_ptr() and c.data_ptr() == cost.c.data_ptr():
             # what forward() checks before it replays this recording without going through any of the above
             self.__dict__["_fast"] = (entry, x_init, cost, cost.C, cost.c, dynamics, x0.data_ptr(), C.data_ptr(), c.data_ptr(),
@@ -454,10 +484,13 @@ class BoxDDP(torch.nn.Module):
         for_out = None
         last_norm = None
         self.__dict__["_best_norm_max"] = None
-        if self.device_loop and not self.verbose and not self.ilqr_verbose and isinstance(cost, QuadCost):
+        cost_chain = False        # the loop ran on dmpc_box_ddp_mlp_cost's chain
+        if self.device_loop and not self.verbose and not self.ilqr_verbose and (
+                isinstance(cost, QuadCost) or self._cost_chain_ok(cost, dynamics, x_init)):
             looped = self._device_loop(x_init, cost, dynamics, u, lo, hi)
             if looped is not None:
                 best, last_norm = looped
+                cost_chain = isinstance(cost, MlpCost)
         for i in range(self.max_iter if best is None else 0):
             with torch.no_grad():
                 if hasattr(dynamics, "fused_ok") and dynamics.fused_ok(x_init, u) and isinstance(cost, QuadCost):
@@ -522,6 +555,8 @@ class BoxDDP(torch.nn.Module):
             leaves = [x_init] + ([cost.Q, cost.p] if isinstance(cost, TiledQuadCost) else [cost.C, cost.c]) + \
                 ([dynamics.AB, dynamics.f0] if isinstance(dynamics, TiledLinDx) else
                  [dynamics.F, dynamics.f] if isinstance(dynamics, LinDx) else [])
+        elif cost_chain:          # (the chain's pair: an MlpCost and a LinDx)
+            leaves = [x_init, cost.Q, cost.p, cost.W1, cost.b1, cost.w2, dynamics.F, dynamics.f]
         if not torch.is_grad_enabled() or (leaves is not None and not any(
                 isinstance(t, torch.Tensor) and t.requires_grad for t in leaves)):
             if self.detach_unconverged:

@@ -11,8 +11,36 @@
 // defines another translation unit's non-template kernels a second time nor emits the ones it does not launch
 #pragma clang attribute push(__attribute__((internal_linkage)), apply_to = function)
 #include "mlp_dx_host.hpp"
+#pragma clang attribute pop
+// (outside the attribute: the two launchers declared here are what mpc_api.hip's chain calls)
+#include "mlp_cost_launch.hpp"
+#pragma clang attribute push(__attribute__((internal_linkage)), apply_to = function)
 #include "mlp_cost_kernels.hpp"
 #pragma clang attribute pop
+
+namespace dmpc {
+
+constexpr int kCostApproxGroups = 2048;      // workgroups of the Taylor model at most: eight per CU, each walks its points
+
+// the two launchers of mlp_cost_launch.hpp: the entry points below and dmpc_box_ddp_mlp_cost's chain (mpc_api.hip) go through them
+void launch_mlp_cost_approx(const MlpCostApproxArgs &a, int act, hipStream_t stream) {
+  const long long groups = (a.P + kMlpWaves - 1) / kMlpWaves;
+  const dim3 grid((unsigned)(groups < kCostApproxGroups ? groups : kCostApproxGroups));
+  const size_t bytes = mlp_cost_lds_bytes(a.m.nx, a.m.nu, a.m.H, kCostApproxWaveFloats);
+  mlp_with_act(act, [&](auto A) {
+    DMPC_LAUNCH_GGL(mlp_cost_approx_kernel<decltype(A)::value>, grid, dim3(64 * kMlpWaves), bytes, stream, a);
+  });
+}
+
+void launch_mlp_cost_search(const MpcFwdArgs &a, const MlpCostModel &m, int act, float *H_next, float *g_next, hipStream_t stream) {
+  const size_t bytes = mlp_cost_lds_bytes(m.nx, m.nu, m.H, H_next != nullptr ? kCostApproxWaveFloats : 0);
+  mlp_with_act(act, [&](auto A) {
+    DMPC_LAUNCH_GGL(mpc_forward_rec_mlp_cost_kernel<decltype(A)::value>, dim3((a.B + kMlpWaves - 1) / kMlpWaves), dim3(64 * kMlpWaves),
+                    bytes, stream, a, m, H_next, g_next);
+  });
+}
+
+}  // namespace dmpc
 
 using namespace dmpc;
 
@@ -25,8 +53,6 @@ int cost_check(int nx, int nu, int H, int act) {
   if (nx > kMlpMaxNx || nu > kMlpMaxNu || H > kCostMaxH) return DMPC_E_UNSUPPORTED;
   return 0;
 }
-
-constexpr int kCostApproxGroups = 2048;      // workgroups of the Taylor model at most: eight per CU, each walks its points
 
 }  // namespace
 
@@ -45,12 +71,7 @@ int dmpc_mlp_cost_approx(int T, int B, int nx, int nu, int n_hidden, int act, co
   const long long P = (long long)T * B;
   if ((size_t)P * (nx + nu) * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;
   const MlpCostApproxArgs aa{P, MlpCostModel{nx, nu, n_hidden, Q, p, W1, b1, w2}, x, u, H_out, g_out, costs_out};
-  const long long groups = (P + kMlpWaves - 1) / kMlpWaves;
-  const dim3 grid((unsigned)(groups < kCostApproxGroups ? groups : kCostApproxGroups));
-  const size_t bytes = mlp_cost_lds_bytes(nx, nu, n_hidden, kCostApproxWaveFloats);
-  mlp_with_act(act, [&](auto A) {
-    DMPC_LAUNCH_GGL(mlp_cost_approx_kernel<decltype(A)::value>, grid, dim3(64 * kMlpWaves), bytes, static_cast<hipStream_t>(stream_), aa);
-  });
+  launch_mlp_cost_approx(aa, act, static_cast<hipStream_t>(stream_));   // (no `done` flag, nothing to clear)
   return (int)hipGetLastError();
 }
 
@@ -71,11 +92,7 @@ int dmpc_mpc_forward_rec_mlp_cost(int T, int B, int nx, int nu, int n_hidden, in
   const MpcFwdArgs fa{T, B, Ks, ks, controls, states, u_lower, u_upper, nullptr, nullptr, F_true, f_true, ls_decay,
                       max_ls_iter, /*ls_cap=*/64, x_out, u_out, u_first, costs, old_costs, alphas, objs, n_ls_iter, info};
   const MlpCostModel m{nx, nu, n_hidden, Q, p, W1, b1, w2};
-  const size_t bytes = mlp_cost_lds_bytes(nx, nu, n_hidden, 0);
-  mlp_with_act(act, [&](auto A) {
-    DMPC_LAUNCH_GGL(mpc_forward_rec_mlp_cost_kernel<decltype(A)::value>, dim3((B + kMlpWaves - 1) / kMlpWaves), dim3(64 * kMlpWaves),
-                    bytes, static_cast<hipStream_t>(stream_), fa, m);
-  });
+  launch_mlp_cost_search(fa, m, act, nullptr, nullptr, static_cast<hipStream_t>(stream_));   // (fa.done: nullptr; no epilogue)
   return (int)hipGetLastError();
 }
 

@@ -28,6 +28,7 @@
 // pre-activations to the bit and the cost difference is exactly 0.
 #pragma once
 #include "mlp_dx_kernels.hpp"
+#include "mlp_cost_launch.hpp"     // MlpCostModel, MlpCostApproxArgs
 
 namespace dmpc {
 
@@ -36,11 +37,6 @@ constexpr int kCostMaxH = mlp_max_hidden(1);
 constexpr int kCostUnits = mlp_units(1);                       // hidden units per lane, at most
 constexpr int kCostApproxWaveFloats = 2 * kCostMaxH;           // the Taylor model's slice: w2 act''(z) and g0's weights
 constexpr int kCostGradCap = 256;                              // partials at most: 7.4 MB at the largest model
-
-struct MlpCostModel {
-  int nx, nu, H;
-  const float *Q, *p, *W1, *b1, *w2;   // device pointers ([ns,ns], [ns], [H,ns], [H], [H]); Q, p: nullptr where a kernel reads neither
-};
 
 // THE byte count of a launch's dynamic LDS
 constexpr size_t mlp_cost_lds_bytes(int nx, int nu, int H, int wave_floats) {
@@ -99,83 +95,98 @@ __device__ __forceinline__ float mlp_cost_tau(const float *x, const float *u, co
   return lane < nx ? x[pt * nx + lane] : (lane < nx + nu ? u[pt * nu + (lane - nx)] : 0.f);
 }
 
-// ---- the Taylor model
-struct MlpCostApproxArgs {
-  long long P;                     // T * B points
-  MlpCostModel m;
-  const float *x, *u;              // [P,nx], [P,nu]
-  float *H_out, *g_out, *costs;    // [P,ns,ns], [P,ns] (both or neither), [P]; any nullptr
-};
-
+// ---- the Taylor model (MlpCostApproxArgs: mlp_cost_launch.hpp)
+// One point's model, by the whole wavefront: the value to costs[pt], g0 to g_out[pt], H to H_out[pt] (costs or the pair may be
+// nullptr).  x, u, H_out, g_out, costs are the arrays' bases.  sw is the wavefront's slice of kCostApproxWaveFloats floats;
+// the two fences order this point's stores to it behind the previous point's reads and in front of this point's.  Both
+// callers - the Taylor model's kernel and the search's epilogue - get their bits from this one instruction sequence.
 template <int ACT>
-__global__ __launch_bounds__(64 * kMlpWaves) void mlp_cost_approx_kernel(const MlpCostApproxArgs a) {
-  extern __shared__ float lds[];
-  const MlpCostLds L = mlp_cost_stage(a.m, lds, kCostApproxWaveFloats);
-  const int lane = threadIdx.x % 64;
-  const int nx = a.m.nx, nu = a.m.nu, ns = nx + nu, H = a.m.H;
+__device__ __forceinline__ void mlp_cost_taylor_point(const MlpCostLds &L, const MlpUnits<kCostUnits> &U, const int nx, const int nu,
+                                                      const int H, const int lane, float *sw, const float *x, const float *u,
+                                                      const size_t pt, float *H_out, float *g_out, float *costs) {
+  const int ns = nx + nu;
   const int lt = lane < ns ? lane : 0;
-  const MlpUnits<kCostUnits> U(lane, H);
-  float *sw = L.wave, *rw = sw + kCostMaxH;
-  const long long stride = (long long)gridDim.x * kMlpWaves;
-  for (long long pt = (long long)blockIdx.x * kMlpWaves + threadIdx.x / 64; pt < a.P; pt += stride) {   // wave-uniform
-    const float tau = mlp_cost_tau(a.x, a.u, (size_t)pt, lane, nx, nu);
-    float z[kCostUnits], sk[kCostUnits], rk[kCostUnits];
-    mlp_layer_from_lanes(L.W1, L.ld, L.b1, U, ns, tau, z);
-    float net = 0.f;
+  float *rw = sw + kCostMaxH;
+  const float tau = mlp_cost_tau(x, u, pt, lane, nx, nu);
+  float z[kCostUnits], sk[kCostUnits], rk[kCostUnits];
+  mlp_layer_from_lanes(L.W1, L.ld, L.b1, U, ns, tau, z);
+  float net = 0.f;
 #pragma unroll
-    for (int k = 0; k < kCostUnits; ++k) {
-      const bool live = U.live(k);
-      float ak, d1, d2;
-      mlp_act2<ACT>(z[k], ak, d1, d2);
-      const float w = live ? L.w2[U.row[k]] : 0.f;
-      net = fmaf(w, live ? ak : 0.f, net);
-      const float y = z[k] - (live ? L.b1[U.row[k]] : 0.f);      // (W1 tau) of this unit
-      sk[k] = live ? w * d2 : 0.f;
-      rk[k] = live ? w * fmaf(-d2, y, d1) : 0.f;
-    }
-    float q = 0.f;
-    for (int j = 0; j < ns; ++j) q = fmaf(L.Q[lt * L.ldq + j], lane_value(tau, j), q);
-    const float part = lane < ns ? cost_row(tau, q, L.p[lt]) : 0.f;
-    const float cost = wave_sum64(part + net);
-    if (a.costs != nullptr && lane == 0) a.costs[pt] = cost;
-    if (a.H_out == nullptr) continue;
+  for (int k = 0; k < kCostUnits; ++k) {
+    const bool live = U.live(k);
+    float ak, d1, d2;
+    mlp_act2<ACT>(z[k], ak, d1, d2);
+    const float w = live ? L.w2[U.row[k]] : 0.f;
+    net = fmaf(w, live ? ak : 0.f, net);
+    const float y = z[k] - (live ? L.b1[U.row[k]] : 0.f);      // (W1 tau) of this unit
+    sk[k] = live ? w * d2 : 0.f;
+    rk[k] = live ? w * fmaf(-d2, y, d1) : 0.f;
+  }
+  float q = 0.f;
+  for (int j = 0; j < ns; ++j) q = fmaf(L.Q[lt * L.ldq + j], lane_value(tau, j), q);
+  const float part = lane < ns ? cost_row(tau, q, L.p[lt]) : 0.f;
+  const float cost = wave_sum64(part + net);
+  if (costs != nullptr && lane == 0) costs[pt] = cost;
+  if (H_out == nullptr) return;
 
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the previous point's reads of the slice are done)
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (the previous point's reads of the slice are done)
 #pragma unroll
-    for (int k = 0; k < kCostUnits; ++k) {
-      if (U.live(k)) {
-        sw[lane + 64 * k] = sk[k];
-        rw[lane + 64 * k] = rk[k];
-      }
+  for (int k = 0; k < kCostUnits; ++k) {
+    if (U.live(k)) {
+      sw[lane + 64 * k] = sk[k];
+      rw[lane + 64 * k] = rk[k];
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    float gj = L.p[lt];
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  float gj = L.p[lt];
 #pragma unroll 4
-    for (int h = 0; h < H; ++h) gj = fmaf(L.W1[h * L.ld + lt], rw[h], gj);
-    if (lane < ns) a.g_out[(size_t)pt * ns + lane] = gj;
-    float *Hp = a.H_out + (size_t)pt * ns * ns;
-    const int ntri = ns * (ns + 1) / 2;
-    for (int e = lane; e < ntri; e += 64) {
-      int i = 0, r = e;
-      while (r >= ns - i) {
-        r -= ns - i;
-        ++i;
-      }
-      const int j = i + r;
-      float acc = 0.5f * (L.Q[i * L.ldq + j] + L.Q[j * L.ldq + i]);
-#pragma unroll 4
-      for (int h = 0; h < H; ++h) acc = fmaf(L.W1[h * L.ld + i] * sw[h], L.W1[h * L.ld + j], acc);
-      Hp[i * ns + j] = acc;
-      Hp[j * ns + i] = acc;
+  for (int h = 0; h < H; ++h) gj = fmaf(L.W1[h * L.ld + lt], rw[h], gj);
+  if (lane < ns) g_out[pt * ns + lane] = gj;
+  float *Hp = H_out + pt * ns * ns;
+  const int ntri = ns * (ns + 1) / 2;
+  for (int e = lane; e < ntri; e += 64) {
+    int i = 0, r = e;
+    while (r >= ns - i) {
+      r -= ns - i;
+      ++i;
     }
+    const int j = i + r;
+    float acc = 0.5f * (L.Q[i * L.ldq + j] + L.Q[j * L.ldq + i]);
+#pragma unroll 4
+    for (int h = 0; h < H; ++h) acc = fmaf(L.W1[h * L.ld + i] * sw[h], L.W1[h * L.ld + j], acc);
+    Hp[i * ns + j] = acc;
+    Hp[j * ns + i] = acc;
   }
 }
 
-// ---- the line search.  a.C, a.c are not read; a.F [T-1,B,nx,ns] and a.f [T-1,B,nx] (or nullptr) are the dense LinDx.
+// In a box-DDP chain: a.clear runs first - thread g of the grid zeroes word g of each range - and a set `done` flag ends the
+// launch before its barrier.
 template <int ACT>
-__global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_cost_kernel(const MpcFwdArgs a, const MlpCostModel m) {
+__global__ __launch_bounds__(64 * kMlpWaves) void mlp_cost_approx_kernel(const MlpCostApproxArgs a) {
   extern __shared__ float lds[];
-  const MlpCostLds L = mlp_cost_stage(m, lds, 0);
+  a.clear.run(blockIdx.x * blockDim.x + threadIdx.x);
+  if (a.done != nullptr && *a.done != 0) return;   // grid-uniform, before the barrier: the iLQR loop has stopped
+  const MlpCostLds L = mlp_cost_stage(a.m, lds, kCostApproxWaveFloats);
+  const int lane = threadIdx.x % 64;
+  const int nx = a.m.nx, nu = a.m.nu, H = a.m.H;
+  const MlpUnits<kCostUnits> U(lane, H);
+  const long long stride = (long long)gridDim.x * kMlpWaves;
+  for (long long pt = (long long)blockIdx.x * kMlpWaves + threadIdx.x / 64; pt < a.P; pt += stride)   // wave-uniform
+    mlp_cost_taylor_point<ACT>(L, U, nx, nu, H, lane, L.wave, a.x, a.u, (size_t)pt, a.H_out, a.g_out, a.costs);
+}
+
+// ---- the line search.  a.C, a.c are not read; a.F [T-1,B,nx,ns] and a.f [T-1,B,nx] (or nullptr) are the dense LinDx.
+// H_next [T,B,ns,ns], g_next [T,B,ns] (BoxDDP's chain; both or neither): the accepted trajectory IS the next iteration's nominal
+// one, so after the search the wavefront walks its T points once more and stores their Taylor model through
+// mlp_cost_taylor_point - bit for bit what mlp_cost_approx_kernel writes for a.x, a.u.  Every lane re-reads only what it stored
+// itself (x element `lane`, control `lane - nx`), so program order is enough.  The launch then stages the wavefront slices
+// (kCostApproxWaveFloats each); without the pair it stages none.  A set a.done ends the launch before its barrier.
+template <int ACT>
+__global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_cost_kernel(const MpcFwdArgs a, const MlpCostModel m,
+                                                                                  float *H_next, float *g_next) {
+  extern __shared__ float lds[];
+  if (a.done != nullptr && *a.done != 0) return;   // grid-uniform, before the barrier: the iLQR loop has stopped
+  const MlpCostLds L = mlp_cost_stage(m, lds, H_next != nullptr ? kCostApproxWaveFloats : 0);
   const int lane = threadIdx.x % 64;
   const int b = blockIdx.x * kMlpWaves + threadIdx.x / 64;
   if (b >= a.B) return;      // (after the only barrier)
@@ -278,6 +289,11 @@ __global__ __launch_bounds__(64 * kMlpWaves) void mpc_forward_rec_mlp_cost_kerne
   }
   if (ls.worse) ls.alpha = cap_alpha_sequential(ls.alpha, a.ls_decay);
   if (lane == 0) search_store<false, false>(a, b, cost, old_cost, ls.alpha, ls.n_pass, search_flags(ls.worse, cost));
+  if (H_next != nullptr) {
+    // the last pass is the accepted one: its states and controls are in a.x, a.u
+    for (int t = 0; t < T; ++t)
+      mlp_cost_taylor_point<ACT>(L, U, nx, nu, m.H, lane, L.wave, a.x, a.u, (size_t)t * B + b, H_next, g_next, nullptr);
+  }
 }
 
 // ---- the parameter gradient.  With v = dL/dg0, r = dL/dcosts at a point, q = W1 v, A = w2 act'(z), Bq = w2 act''(z) q:

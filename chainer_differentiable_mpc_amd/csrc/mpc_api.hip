@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "../../include/dmpc.h"
+#include "../../include/dmpc_mlp_cost.h"
 #include "api_util.hpp"
 #include "knobs.hpp"
 #include "costate_args.hpp"
@@ -23,6 +24,7 @@
 #include "mpc_coupled.hpp"
 #include "mpc_kernels.hpp"
 #include "mlp_dx_launch.hpp"
+#include "mlp_cost_launch.hpp"
 
 namespace dmpc {
 
@@ -738,6 +740,27 @@ static DdpWs ddp_layout(int T, int B, int nx, int nu) {
   return w;
 }
 
+// The stage cost of a box-DDP chain: a QuadCost's C [T,B,ns,ns], c [T,B,ns], or a packed MlpCost (mlp_cost_launch.hpp), whose
+// Taylor model the chain forms itself - in C_hat, c_hat behind the workspace of ddp_layout.
+struct DdpCost {
+  const float *C = nullptr, *c = nullptr;   // QuadCost
+  bool net = false;                         // MlpCost: m, act, and whether the search also stores the next Taylor model
+  MlpCostModel m{};
+  int act = 0;
+  bool search_approximates = false;
+};
+struct DdpCostWs {
+  size_t C_hat, c_hat, total;
+};
+static DdpCostWs ddp_cost_layout(int T, int B, int nx, int nu) {
+  const size_t ns = nx + nu, TB = (size_t)T * B;
+  DdpCostWs w;
+  w.C_hat = ddp_layout(T, B, nx, nu).total;
+  w.c_hat = w.C_hat + round_up(TB * ns * ns * sizeof(float), 256);
+  w.total = w.c_hat + round_up(TB * ns * sizeof(float), 256);
+  return w;
+}
+
 // dmpc_mpc_step_status: one workgroup reduces the step's per-trajectory words (include/dmpc.h)
 __global__ __launch_bounds__(1024) void mpc_step_status_kernel(int B, const int32_t *__restrict__ info, const int32_t *__restrict__ nqp,
                                                                const float *__restrict__ alphas, int32_t *__restrict__ status) {
@@ -979,16 +1002,24 @@ size_t dmpc_box_ddp_workspace_bytes(int T, int B, int nx, int nu) {
   return ddp_layout(T, B, nx, nu).total;
 }
 
-int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float *C, const float *c, const float *F,
-                 const float *f, int dyn_kind, const float *dyn_params, const float *u_init, const float *u_lower,
-                 const float *u_upper, float eps, int not_improved_lim, float ls_decay, int max_ls_iter,
-                 float best_cost_eps, int max_iter, int n_qp_iter_max, int scrambled_norm, int batch_coupled,
-                 float *x_best, float *u_best, float *costs_best, float *du_norm_best, float *du_norm_last,
-                 int32_t *state, void *ws, size_t ws_bytes, int32_t *info, dmpc_stream_t stream_) {
+}  // extern "C"
+
+namespace dmpc {
+
+// The chain of dmpc_box_ddp (include/dmpc.h) and dmpc_box_ddp_mlp_cost (include/dmpc_mlp_cost.h): the arguments of the former with
+// the stage cost as a descriptor.  With a QuadCost the checks, routes and launches are dmpc_box_ddp's own.  With an MlpCost
+// (dyn_kind 0 only; its caller has checked the model) every iteration forms the Taylor model C_hat, c_hat at the nominal trajectory
+// (mlp_cost_approx_kernel behind the rollout, or the previous search's epilogue), sweeps on it and searches on the network.
+static int box_ddp_chain(int T, int B, int nx, int nu, const float *x_init, const DdpCost &cost, const float *F,
+                         const float *f, int dyn_kind, const float *dyn_params, const float *u_init, const float *u_lower,
+                         const float *u_upper, float eps, int not_improved_lim, float ls_decay, int max_ls_iter,
+                         float best_cost_eps, int max_iter, int n_qp_iter_max, int scrambled_norm, int batch_coupled,
+                         float *x_best, float *u_best, float *costs_best, float *du_norm_best, float *du_norm_last,
+                         int32_t *state, void *ws, size_t ws_bytes, int32_t *info, dmpc_stream_t stream_) {
   if (T <= 1 || B <= 0 || nx <= 0 || nu <= 0 || max_iter <= 0 || n_qp_iter_max <= 0) return DMPC_E_BADARG;
   if (batch_coupled && n_qp_iter_max > kSyncQpIterMax) return DMPC_E_UNSUPPORTED;
-  if (!x_init || !C || !c || !u_init || !u_lower || !u_upper || !x_best || !u_best || !costs_best || !du_norm_best ||
-      !du_norm_last || !state || !ws)
+  if (!x_init || (!cost.net && (!cost.C || !cost.c)) || !u_init || !u_lower || !u_upper || !x_best || !u_best || !costs_best ||
+      !du_norm_best || !du_norm_last || !state || !ws)
     return DMPC_E_BADARG;
   if (dyn_kind == 0 && !F) return DMPC_E_BADARG;
   if (dyn_kind == 1 && (!dyn_params || nx != 3 || nu != 1)) return DMPC_E_BADARG;
@@ -1011,11 +1042,19 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   }
   // (round 5: shapes that run on the tiled kernels - more than 8 controls / 64 columns - too: their matrices live in w.tiled)
   if ((size_t)T * B * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;  // 32-bit indices in the bookkeeping
-  if (!aligned16(C) || !aligned16(c) || !aligned16(F) || !aligned16(f) || !aligned16(ws)) return DMPC_E_BADARG;
+  if (!aligned16(cost.C) || !aligned16(cost.c) || !aligned16(F) || !aligned16(f) || !aligned16(ws)) return DMPC_E_BADARG;
   const DdpWs w = ddp_layout(T, B, nx, nu);
-  if (ws_bytes < w.total) return DMPC_E_WORKSPACE;
+  const DdpCostWs wc = cost.net ? ddp_cost_layout(T, B, nx, nu) : DdpCostWs{0, 0, w.total};
+  if (ws_bytes < wc.total) return DMPC_E_WORKSPACE;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   char *base = static_cast<char *>(ws);
+  // MlpCost: the Taylor model at the nominal trajectory is what the sweep reads as C, c (the search reads neither)
+  float *C_hat = cost.net ? reinterpret_cast<float *>(base + wc.C_hat) : nullptr;
+  float *c_hat = cost.net ? reinterpret_cast<float *>(base + wc.c_hat) : nullptr;
+  const float *C = cost.net ? C_hat : cost.C, *c = cost.net ? c_hat : cost.c;
+  // ... and the search can store the next one while it stores the trajectory (search_approximates): the rollout and the
+  // Taylor model's launch then run for the first iteration only
+  const bool cost_lin = cost.net && cost.search_approximates;
   auto fp = [&](size_t off) { return reinterpret_cast<float *>(base + off); };
   auto ip = [&](size_t off) { return reinterpret_cast<int32_t *>(base + off); };
   float *xs = fp(w.xs), *c_back = fp(w.c_back), *Ks = fp(w.Ks), *ks = fp(w.ks), *x_new = fp(w.x_new);
@@ -1042,7 +1081,7 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   // through the rollout kernel's own two functions, so both settings return the same bits.  The re-centring stays the sweep's.
   const bool mlp = dyn_kind == 2, mlp_lin = mlp && mlp_search_lin != 0;
   const MlpModel mlp_model = mlp ? mlp_model_packed(nx, nu, mlp_hidden, mlp_residual, F) : MlpModel{};
-  const bool ping_pong = fuse_lin || mlp_lin;   // the nominal states alternate between the two state buffers
+  const bool ping_pong = fuse_lin || mlp_lin || cost_lin;   // the nominal states alternate between the two state buffers
   float *x_buf[2] = {xs, x_new};
   const bool copy_here = B <= kDdpCopyHereMaxB && rows * (size_t)(nx + nu) <= kDdpCopyHereMaxElems;
   // MPCstep.forward with need_expand: f_hat = None                                        mpc_step.py:305-328
@@ -1071,8 +1110,9 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   fused_select = fuse_lin && copy_here && (sweep[0].kind == MpcKernel::kStream || sweep[0].kind == MpcKernel::kRing);
   sweep[1] = mpc_sweep_route(sweep_call(nx, nu, back_args(u_buf[1], x_new), fused_select, true));
   // (MlpDx: the network's search is no row of mpc_search_route - it is this chain's branch on dyn_kind, checked above)
-  search[0] = mlp ? MpcSearchRoute{0} : mpc_search_route(search_call(nx, nu, fwd_args(u_init, xs, x_new, u_buf[1], u1, costs)));
-  search[1] = mlp ? MpcSearchRoute{0} : mpc_search_route(search_call(nx, nu, fwd_args(u_buf[1], x_new, xs, u_buf[0], u1, costs)));
+  const bool net_search = mlp || cost.net;   // (MlpCost: likewise, its search is this chain's branch on the cost)
+  search[0] = net_search ? MpcSearchRoute{0} : mpc_search_route(search_call(nx, nu, fwd_args(u_init, xs, x_new, u_buf[1], u1, costs)));
+  search[1] = net_search ? MpcSearchRoute{0} : mpc_search_route(search_call(nx, nu, fwd_args(u_buf[1], x_new, xs, u_buf[0], u1, costs)));
   for (const int code : {sweep[0].code, search[0].code, sweep[1].code, search[1].code})
     if (code != 0) return code;
   DdpSelectArgs sa{};
@@ -1111,9 +1151,14 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
                           it == 0 ? clear : ChainClear{}};
         launch_mlp_rollout(ra, mlp_act, stream);
       }
-    } else {
+    } else if (it == 0 || !cost_lin) {
       DMPC_LAUNCH_GGL(lin_rollout_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, T, B, nx, nu, x_init, u_cur, F,
                          f, xs_it, it == 0 ? nullptr : done, it == 0 ? clear : ChainClear{});
+      if (cost.net) {   // (never the chain's first launch: nothing to clear)
+        const MlpCostApproxArgs ca{(long long)rows, cost.m, xs_it, u_cur, C_hat, c_hat, nullptr, it == 0 ? nullptr : done,
+                                   ChainClear{}};
+        launch_mlp_cost_approx(ca, cost.act, stream);
+      }
     }
     MpcBackArgs ba = back_args(u_cur, xs_it);
     if (sweep[k].needs_scratch) ba.tiled_scratch = fp(w.tiled);
@@ -1140,6 +1185,9 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
       if (rc != 0) return rc;
       if (mlp) {
         launch_mlp_search(fa, mlp_model, mlp_act, stream);
+        rc = (int)hipGetLastError();
+      } else if (cost.net) {
+        launch_mlp_cost_search(fa, cost.m, cost.act, cost_lin ? C_hat : nullptr, cost_lin ? c_hat : nullptr, stream);
         rc = (int)hipGetLastError();
       } else {
         rc = search[k].launch({fa, nx, nu}, stream);
@@ -1171,6 +1219,54 @@ int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float 
   DMPC_LAUNCH_GGL(box_ddp_summary_kernel, dim3(1), dim3(1024), 0, stream, rows * nu, B, u_init, u_lower, u_upper, info,
                      (int)DMPC_INFO_NONFINITE, du_norm_best, eps, state, sa, fused_select && !split_last ? 1 : 0);
   return (int)hipGetLastError();
+}
+
+}  // namespace dmpc
+
+extern "C" {
+
+int dmpc_box_ddp(int T, int B, int nx, int nu, const float *x_init, const float *C, const float *c, const float *F,
+                 const float *f, int dyn_kind, const float *dyn_params, const float *u_init, const float *u_lower,
+                 const float *u_upper, float eps, int not_improved_lim, float ls_decay, int max_ls_iter,
+                 float best_cost_eps, int max_iter, int n_qp_iter_max, int scrambled_norm, int batch_coupled,
+                 float *x_best, float *u_best, float *costs_best, float *du_norm_best, float *du_norm_last,
+                 int32_t *state, void *ws, size_t ws_bytes, int32_t *info, dmpc_stream_t stream) {
+  DdpCost cost;
+  cost.C = C;
+  cost.c = c;
+  return box_ddp_chain(T, B, nx, nu, x_init, cost, F, f, dyn_kind, dyn_params, u_init, u_lower, u_upper, eps, not_improved_lim,
+                       ls_decay, max_ls_iter, best_cost_eps, max_iter, n_qp_iter_max, scrambled_norm, batch_coupled, x_best, u_best,
+                       costs_best, du_norm_best, du_norm_last, state, ws, ws_bytes, info, stream);
+}
+
+size_t dmpc_box_ddp_mlp_cost_workspace_bytes(int T, int B, int nx, int nu) {
+  if (T <= 0 || B <= 0 || nx <= 0 || nu <= 0) return 0;
+  return ddp_cost_layout(T, B, nx, nu).total;
+}
+
+int dmpc_box_ddp_mlp_cost(int T, int B, int nx, int nu, const float *x_init, const float *cost_packed, int n_hidden, int act,
+                          int search_approximates, const float *F, const float *f, int dyn_kind, const float *dyn_params,
+                          const float *u_init, const float *u_lower, const float *u_upper, float eps, int not_improved_lim,
+                          float ls_decay, int max_ls_iter, float best_cost_eps, int max_iter, int n_qp_iter_max,
+                          int scrambled_norm, int batch_coupled, float *x_best, float *u_best, float *costs_best,
+                          float *du_norm_best, float *du_norm_last, int32_t *state, void *ws, size_t ws_bytes, int32_t *info,
+                          dmpc_stream_t stream) {
+  if (T <= 1 || B <= 0 || nx <= 0 || nu <= 0 || n_hidden <= 0 || max_iter <= 0 || n_qp_iter_max <= 0) return DMPC_E_BADARG;
+  if (!cost_packed || !aligned16(cost_packed) || !F) return DMPC_E_BADARG;
+  if (search_approximates != 0 && search_approximates != 1) return DMPC_E_BADARG;
+  // dyn_kind 1, 2 (the pendulum, an MlpDx) are reserved: their searches would have to evaluate this cost
+  if (dyn_kind != 0 || batch_coupled != 0) return DMPC_E_UNSUPPORTED;
+  if (!dmpc_mlp_cost_supported(nx, nu, n_hidden, act)) return DMPC_E_UNSUPPORTED;
+  // (the limit of dmpc_mlp_cost_approx)
+  if ((size_t)T * B * (nx + nu) * (nx + nu) >= ((size_t)1 << 31)) return DMPC_E_UNSUPPORTED;
+  DdpCost cost;
+  cost.net = true;
+  cost.m = mlp_cost_model_packed(nx, nu, n_hidden, cost_packed);
+  cost.act = act;
+  cost.search_approximates = search_approximates != 0;
+  return box_ddp_chain(T, B, nx, nu, x_init, cost, F, f, dyn_kind, dyn_params, u_init, u_lower, u_upper, eps, not_improved_lim,
+                       ls_decay, max_ls_iter, best_cost_eps, max_iter, n_qp_iter_max, scrambled_norm, batch_coupled, x_best, u_best,
+                       costs_best, du_norm_best, du_norm_last, state, ws, ws_bytes, info, stream);
 }
 
 int dmpc_mpc_step_backward(int T, int B, int nx, int nu, const float *C_hat, const float *c_hat,

@@ -15,6 +15,15 @@ is a valid callable cost on every route that takes one.  On the GPU, at a size t
     (`dmpc_mlp_cost_param_grad`): gradients reach Q, p, W1, b1, w2; the Hessian is a constant of the graph (approximate.py:75)
     and x, u receive none.  "live" (the default) leaves a call that wants a gradient to `approximate_cost`'s autograd route.
 
+`BoxDDP` drives those kernels from its host loop.  With `device_loop=True` (the last keyword; off by default) it runs the whole
+iLQR loop as one chain of launches instead (`dmpc_box_ddp_mlp_cost`), where the chain serves the problem - GPU tensors, a
+supported size, a `LinDx` with a dense F, T >= 2, no `batch_coupled` and no verbose output; anything else keeps the host loop.
+The chain takes the weights as ONE flat float32 buffer, `packed_weights`:
+
+    [Q (ns*ns) | p (ns) | W1 (H*ns) | b1 (H) | w2 (H)]
+
+kept per device and refilled in place by one launch before every solve and every replay of a recorded one.
+
 The weights go to the library as device pointers on every call: nothing is read back and nothing is cached, so an optimiser step
 in place is seen by the next call.  CPU tensors or a size outside the limits take the autograd route whatever the keyword says.
 
@@ -33,13 +42,27 @@ from .mlp_dx import ACTIVATIONS, PARAM_GRADS, _ACT_FN
 
 
 class MlpCost(torch.nn.Module):
-    def __init__(self, n_state, n_ctrl, n_hidden, activation="softplus", Q=None, p=None, seed=None, param_grad="live"):
+    """c(tau) = 1/2 tau' Q tau + p' tau + w2' act(W1 tau + b1) (the module's docstring has the routes).
+
+    `device_loop` (the last keyword, default False): `BoxDDP` runs its whole iLQR loop with this cost as one chain of launches
+    (`dmpc_box_ddp_mlp_cost`) where that chain serves the problem - GPU tensors, a supported size that is the solver's, a `LinDx`
+    with a dense F, T >= 2, no `batch_coupled`, no verbose output; False, or any other problem: the host loop over the kernels.
+    The chain reads the weights from `packed_weights(device)`, ONE flat float32 buffer per device in the order
+
+        [Q (ns*ns) | p (ns) | W1 (H*ns) | b1 (H) | w2 (H)]
+
+    refilled in place by one launch on every call, at the same address each time."""
+
+    def __init__(self, n_state, n_ctrl, n_hidden, activation="softplus", Q=None, p=None, seed=None, param_grad="live",
+                 device_loop=False):
         super().__init__()
         if activation not in ACTIVATIONS:
             raise ValueError("MlpCost: unknown activation %r (one of %s)" % (activation, ", ".join(ACTIVATIONS)))
         if param_grad not in PARAM_GRADS:
             raise ValueError("MlpCost: param_grad is \"live\" or \"device\", found %r" % (param_grad,))
         self.activation, self.param_grad = activation, param_grad
+        self.device_loop = bool(device_loop)
+        self._packed = {}           # device -> the flat weight buffer of `packed_weights` (no parameter, no buffer, not pickled)
         self.n_state, self.n_ctrl, self.n_hidden = int(n_state), int(n_ctrl), int(n_hidden)
         if self.n_hidden < 1:
             raise ValueError("MlpCost: the network needs at least one hidden unit, found %r" % (n_hidden,))
@@ -87,9 +110,20 @@ class MlpCost(torch.nn.Module):
         return m
 
     def extra_repr(self):
-        return "n_state=%d, n_ctrl=%d, n_hidden=%d, activation=%s%s" % (
+        return "n_state=%d, n_ctrl=%d, n_hidden=%d, activation=%s%s%s" % (
             self.n_state, self.n_ctrl, self.n_hidden, self.activation,
-            ", param_grad=%s" % self.param_grad if self.param_grad != "live" else "")
+            ", param_grad=%s" % self.param_grad if self.param_grad != "live" else "",
+            ", device_loop=True" if self.device_loop else "")
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_packed"] = {}       # a copy or an unpickled model packs into a buffer of its own
+        return state
+
+    def __setstate__(self, state):
+        state.setdefault("device_loop", False)      # (pickled before the keyword existed)
+        state.setdefault("_packed", {})
+        super().__setstate__(state)
 
     @property
     def act_code(self):
@@ -133,6 +167,22 @@ class MlpCost(torch.nn.Module):
     def device_weights(self, device):
         """(Q, p, W1, b1, w2) as the kernels take them - contiguous float32 on `device`; made on every call, never kept"""
         return tuple(_lib.f32c(w.detach(), device) for w in self._weights())
+
+    def packed_weights(self, device):
+        """[Q | p | W1 | b1 | w2] as ONE flat float32 buffer on `device`, the `cost_packed` of `dmpc_box_ddp_mlp_cost`.  The buffer
+        is kept per device and refilled in place by one launch on every call: its address is stable (a recorded hipGraph keeps
+        reading it), its contents are the parameters' of this moment."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        parts = [w.detach().reshape(-1) for w in self._weights()]
+        if any(w.dtype != torch.float32 or w.device != device for w in parts):
+            parts = [w.to(device=device, dtype=torch.float32) for w in parts]
+        buf = self._packed.get(device)
+        if buf is None or buf.numel() != sum(w.numel() for w in parts):
+            buf = self._packed[device] = torch.empty(sum(w.numel() for w in parts), dtype=torch.float32, device=device)
+        torch.cat(parts, out=buf)
+        return buf
 
     def _launch_approx(self, x, u, weights, want_model):
         T, B = x.shape[0], x.shape[1]

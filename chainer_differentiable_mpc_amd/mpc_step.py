@@ -28,7 +28,8 @@ import torch
 from . import _lib
 from .lqr_recursion import _as_tensor, _device_of, _workspace, raise_info
 from .lqr_shared import SHARED_F_TIME, SHARED_FVEC_TIME
-from .util import LinDx, QuadCost, bdot, bmv, bquad, clamp, get_cost
+from .pnqp import pnqp_device
+from .util import LinDx, QuadCost, batch_lu_solve, bdot, bmv, bquad, clamp, get_cost
 
 LqrBackOut = namedtuple("lqrBackOut", "n_total_qp_iter")
 LqrForOut = namedtuple("lqrForOut", "objs full_du_norm alpha_du_norm mean_alphas costs")
@@ -322,6 +323,8 @@ class MPCstep:
         assert F.shape[0] in (T - 1, T) and list(F.shape[1:]) == [B, nx, ns], "F_hat dim mismatch"
         assert not bool(torch.isnan(self._u).any())
         assert bool((self._lo <= self._hi).all()), " lower is larger than upper"
+        if T == 1:
+            return self._backward_rec_single(C, c)
         Ks = torch.empty((T, B, nu, nx), dtype=torch.float32, device=d)
         ks = torch.empty((T, B, nu), dtype=torch.float32, device=d)
         nqp = torch.empty((B,), dtype=torch.int32, device=d)
@@ -339,6 +342,24 @@ class MPCstep:
         _lib.check(rc, "dmpc_mpc_backward_rec")
         self.n_qp_iter = nqp
         self.info = info
+        assert not bool(torch.isnan(ks).any()) and not bool(torch.isnan(Ks).any())     # mpc_step.py:161-162
+        return self._out(Ks), self._out(ks), LqrBackOut(n_total_qp_iter=int(nqp.max().item()))
+
+    def _backward_rec_single(self, C, c):
+        """T = 1: there is no dynamics step, so the recursion is its last step alone (mpc_step.py:105-107, 130-162) - the box
+        QP in the controls by `dmpc_pnqp` (cold start, as the reference's first QP) and the gain from the factor of its free
+        block, rows of clamped controls zeroed.  `dmpc_mpc_backward_rec` serves T >= 2."""
+        B, nx, nu, d = self.n_batch, self.n_state, self.n_ctrl, self._dev
+        Quu, Qux, qu = C[0][:, nx:, nx:].contiguous(), C[0][:, nx:, :nx], c[0][:, nx:].contiguous()
+        info = torch.zeros(B, dtype=torch.int32, device=d)
+        k, fac, piv, free, iters = pnqp_device(Quu, qu, (self._lo[0] - self._u[0]).contiguous(), (self._hi[0] - self._u[0]).contiguous(),
+                                               None, self.n_qp_iter_max, info, self.batch_coupled)          # :136-141
+        Qux = (Qux * free[:, :, None]).contiguous()                                                          # :147-150
+        K = -(Qux / fac) if nu == 1 else -batch_lu_solve((fac, piv), Qux)                                    # :154, :157
+        nqp = (1 + iters).to(torch.int32)                                                                    # :145
+        self.n_qp_iter = nqp
+        self.info = info
+        Ks, ks = K[None].contiguous(), k[None].contiguous()
         assert not bool(torch.isnan(ks).any()) and not bool(torch.isnan(Ks).any())     # mpc_step.py:161-162
         return self._out(Ks), self._out(ks), LqrBackOut(n_total_qp_iter=int(nqp.max().item()))
 

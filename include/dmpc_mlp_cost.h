@@ -41,6 +41,29 @@
  *   mlp_cost_param_grad_reduce_kernel adds the G partials per element in ascending order.  No atomics: the result is bit-equal
  *   from call to call and depends on (T B, nx, nu, H) and the data alone.  ws NULL or shorter than
  *   dmpc_mlp_cost_param_grad_workspace_bytes (0 for a size the kernels refuse): DMPC_E_WORKSPACE.
+ *
+ * dmpc_box_ddp_mlp_cost: dmpc_box_ddp (dmpc.h) with this cost in place of a QuadCost's C, c, under a dense LinDx F [T-1,B,nx,ns],
+ *   f [T-1,B,nx] or NULL: the whole iLQR loop as one chain of launches with its stop tests on the device.  No allocation, no host
+ *   synchronisation, no read-back; `state`, `info` and the five outputs mean exactly what they mean in dmpc_box_ddp.
+ *   cost_packed is ONE device array of contiguous float32, 16-byte aligned:
+ *       [Q (ns*ns) | p (ns) | W1 (H*ns) | b1 (H) | w2 (H)]
+ *   Every launch reads it and nothing is cached: an optimiser step in place is seen by the next call and by a replayed hipGraph.
+ *   Launches of an iteration (after the stop they are no-ops through the device flag; the chain's first launch clears the
+ *   chain's words):
+ *     search_approximates = 0, five: lin_rollout_kernel; mlp_cost_approx_kernel<act> into the workspace's C_hat, c_hat; the
+ *       backward sweep of dmpc_box_ddp's dyn_kind 0 on C_hat, c_hat, F (it re-centres c itself); mpc_forward_rec_mlp_cost_kernel<act>;
+ *       the bookkeeping (box_ddp_select_kernel, and box_ddp_keep_kernel for the larger problems).
+ *     search_approximates = 1: the first iteration as above; the search also stores the Taylor model of the trajectory it
+ *       accepts - the next iteration's nominal one - through the function mlp_cost_approx_kernel forms it with, and the states
+ *       it leaves are lin_rollout_kernel's to the bit (the same sums in the same order).  Every later iteration is three
+ *       launches: sweep, search, bookkeeping; the nominal states alternate between two state buffers.  Every output and `state`
+ *       is bit for bit that of search_approximates = 0.
+ *   Then box_ddp_summary_kernel.  The workspace is dmpc_box_ddp's, then C_hat [T,B,ns,ns] and c_hat [T,B,ns]
+ *   (dmpc_box_ddp_mlp_cost_workspace_bytes; 0 for a non-positive size).
+ *   DMPC_E_BADARG: what dmpc_box_ddp reports so; cost_packed NULL or not 16-byte aligned; search_approximates other than 0 or 1;
+ *   F NULL.  DMPC_E_UNSUPPORTED: dyn_kind != 0 - the codes 1 (the pendulum) and 2 (MlpDx) are reserved: with this cost either
+ *   needs a search kernel that evaluates both models, which does not exist; batch_coupled != 0; a size or `act` that
+ *   dmpc_mlp_cost_supported refuses; T B ns^2 >= 2^31.  DMPC_E_WORKSPACE: ws shorter than the query.  dyn_params is not read.
  */
 #ifndef DMPC_MLP_COST_H_
 #define DMPC_MLP_COST_H_
@@ -66,6 +89,14 @@ int dmpc_mlp_cost_param_grad(int T, int B, int nx, int nu, int n_hidden, int act
                              const float *w2, const float *x, const float *u, const float *grad_g, const float *grad_costs,
                              float *dQ, float *dp, float *dW1, float *db1, float *dw2, void *ws, size_t ws_bytes,
                              dmpc_stream_t stream);
+size_t dmpc_box_ddp_mlp_cost_workspace_bytes(int T, int B, int nx, int nu);
+int dmpc_box_ddp_mlp_cost(int T, int B, int nx, int nu, const float *x_init, const float *cost_packed, int n_hidden, int act,
+                          int search_approximates, const float *F, const float *f, int dyn_kind, const float *dyn_params,
+                          const float *u_init, const float *u_lower, const float *u_upper, float eps, int not_improved_lim,
+                          float ls_decay, int max_ls_iter, float best_cost_eps, int max_iter, int n_qp_iter_max,
+                          int scrambled_norm, int batch_coupled, float *x_best, float *u_best, float *costs_best,
+                          float *du_norm_best, float *du_norm_last, int32_t *state, void *ws, size_t ws_bytes, int32_t *info,
+                          dmpc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,11 @@
 """One `BoxDDP` solve, and one solve plus gradient, under a learned stage cost (`MlpCost`) with a dense `LinDx`,
-three ways on equal weights in the same run:
+four ways on equal weights in the same run:
   live    - the `MlpCost` module as it is (param_grad="live"): the Taylor model of one launch and the line search inside its
             kernel wherever no gradient is wanted; the final gradient model through `approximate_cost`'s autograd route;
   device  - `MlpCost(param_grad="device")`: the final gradient model too is one launch, its backward `dmpc_mlp_cost_param_grad`;
+  chain   - `MlpCost(device_loop=True, param_grad="device")`: the iLQR loop itself as one chain of launches with one read-back
+            (`dmpc_box_ddp_mlp_cost`, replayed from the solver's hipGraph from the third call on); the gradient as "device".
+            Its yardstick is "device" - the host loop over the same kernels - not the lambda (`chain_over_device`);
   lambda  - the same module behind `lambda tau: cost(tau)`: T (1 + ns) autograd calls per iLQR iteration and the line search as a
             Python loop - the only route a cost that is not quadratic had before `MlpCost` (the baseline).
 The variants take turns solve by solve (one round = one solve of each), after `--warmup` rounds; reported per variant: the
@@ -21,7 +24,7 @@ import torch  # noqa: E402
 
 from chainer_differentiable_mpc_amd import BoxDDP, LinDx, MlpCost, synthetic  # noqa: E402
 
-VARIANTS = ("live", "device", "lambda")
+VARIANTS = ("live", "device", "chain", "lambda")
 
 
 def run_case(nx, nu, H, B, T, iters, warmup, grad):
@@ -32,7 +35,8 @@ def run_case(nx, nu, H, B, T, iters, warmup, grad):
     lin = 0.3 * torch.randn(nx + nu, generator=gen)
     routes = {}
     for tag in VARIANTS:
-        m = MlpCost(nx, nu, H, seed=0, p=lin, param_grad="device" if tag == "device" else "live").cuda()
+        m = MlpCost(nx, nu, H, seed=0, p=lin, param_grad="device" if tag in ("device", "chain") else "live",
+                    device_loop=tag == "chain").cuda()
         cost = (lambda tau, m=m: m(tau)) if tag == "lambda" else m
         solver = BoxDDP(T, -0.5, 0.5, B, nx, nu, None, max_iter=10, quiet=True, detach_unconverged=False,
                         update_dynamics=False)      # the gradient goes to the cost
@@ -75,6 +79,7 @@ def run_case(nx, nu, H, B, T, iters, warmup, grad):
         out[tag + "_speedup"] = None
     for tag in VARIANTS:
         out[tag + "_speedup"] = out["lambda_ms"] / out[tag + "_ms"]
+    out["chain_over_device"] = out["device_ms"] / out["chain_ms"]          # the chain against the host loop over the same kernels
     return out
 
 
